@@ -19,7 +19,10 @@ captured once into a HIP graph and replayed, like the reference's decode path
 timed region.  Data is synthetic: random-init weights with the reference's dummy-loader recipe, a
 random-permutation page table (worst case for HBM), context length CTX per request.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (paged decode attention):
+Prints ONE JSON line (rank 0).  The plain command sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, `config`); `--dump-outputs DIR` adds the last timed step's logits and sampled token ids as DIR/*.npy (the
+inputs are seeded: two builds can be compared output for output).  Everything below is reported with `--full` only, measured
+after the timed steps.  `roofline` is for the dominant kernel (paged decode attention):
 achieved = algorithmic bytes per launch / its average launch duration, measured with HIP events around every launch of it
 in an instrumented (eager) pass over the same K steps (`roofline.method` says which figure is primary and gives the
 in-step difference-of-graphs figure beside it).
@@ -94,9 +97,16 @@ def parse():
                          "model file gets from the drop-in classes) or this repo's fused producers; the other one is reported "
                          "beside it (value_fused / value_dropin)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement (the other call order, rooflines, TTFT, all-reduce "
+                         "report, CPU baseline, the other BASELINE configs) and report them in the same line; without it the run "
+                         "sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the logits of the batch and the sampled token ids) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of BASELINE configs 2, 4 and 5 (one rank emulated) that the default N=1 "
+                    help="with --full: skip the short runs of BASELINE configs 2, 4 and 5 (one rank emulated) that the N=1 "
                          "invocation reports beside the headline")
     return ap.parse_args()
 
@@ -149,7 +159,8 @@ class DecodeLoop:
     def __init__(self, net, runner, backend, B, ctx, device, use_graph=True):
         from sglang_npu_amd.harness import ForwardBatch, ForwardMode
         self.net, self.runner, self.backend, self.B, self.device = net, runner, backend, B, device
-        self.input_ids = torch.randint(0, 10000, (B,), device=device)
+        # seeded like the weights and the KV pool: two runs with the same arguments see the same inputs (--dump-outputs)
+        self.input_ids = torch.randint(0, 10000, (B,), device=device, generator=torch.Generator(device=device).manual_seed(4321))
         self.seq_lens = torch.full((B,), ctx, dtype=torch.int64, device=device)  # includes the token being decoded
         self.positions = self.seq_lens - 1
         self.req_pool_indices = torch.arange(B, dtype=torch.int64, device=device)
@@ -175,6 +186,7 @@ class DecodeLoop:
         logits = self.net(self.input_ids, self.positions, self.fb)
         from sglang_npu_amd.layers import greedy_sample
         self.next_ids.copy_(greedy_sample(logits))
+        self.logits = logits  # of the last pass; under graph replay the captured pass's tensor, rewritten by every replay
 
     def capture(self):
         self.backend.init_cuda_graph_state(self.B, self.B)
@@ -213,6 +225,25 @@ class DecodeLoop:
         self.seq_lens += 1
         self.cur_len += 1
         self._refresh()
+
+
+DUMP_MAX_ELEMS = 12 << 20  # float32 elements of one dumped array (48 MiB): the whole dump stays under 64 MB
+
+
+def dump_outputs(path, loop):
+    """--dump-outputs: what the last step of the loop handed back -- the logits of the batch (float32) and the greedily sampled
+    token ids (float64, exact) -- as <path>/<name>.npy.  An array above DUMP_MAX_ELEMS elements is cut to a fixed sample of
+    its flattened form (seeded, so the same elements from run to run and from build to build)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = {"logits": loop.logits.detach().float().cpu().numpy(),
+              "next_token_ids": loop.next_ids.detach().cpu().numpy().astype(np.float64)}
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def time_attention_kernel(loop, steps):
@@ -793,7 +824,7 @@ def other_configs():
              ["--model", "llama3-70b", "--emulate-tp", "8"])]
     out = []
     for name, extra in runs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline",
                "--no-other-configs"] + extra
         try:
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
@@ -948,7 +979,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     others = None
-    if (world == 1 and args.gpus == 1 and not args.no_other_configs and args.model == "llama3-8b" and
+    if (args.full and world == 1 and args.gpus == 1 and not args.no_other_configs and args.model == "llama3-8b" and
             args.quant == "w8a8_fp8" and args.emulate_tp == 0 and args.layers is None and args.kv_dtype == "auto"):
         others = other_configs()
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -1052,6 +1083,8 @@ def main():
     # ---- the contract's timed region: W warm-up steps, then exactly K steps between barriers
     set_call_order(want_fused)
     elapsed = timed(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop)
     ms_per_step = elapsed / args.steps * 1e3
     value = args.batch * args.steps / elapsed
     order_name = ("this repo's fused entry points (norm+quant / RoPE+KV-write / SiLU+quant producers, GEMM epilogues inside their "
@@ -1075,6 +1108,16 @@ def main():
         "dist_backend": torch.distributed.get_backend() if dist_on else None,
     }
     checkpoint(out)
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist_on:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+
+    if not args.full:  # the plain run ends with its headline; everything below is a side measurement
+        return finish()
 
     # ---- the other call order, and a device-synchronised per-step median (bench_one_batch.py:380-424 shape)
     other = None
@@ -1372,11 +1415,7 @@ def main():
         elif "error" not in res:
             res["error"] = "another rank could not build the model"
         out["config5_llama3_70b"] = res
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist_on:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -48,6 +48,16 @@ def test_a_hung_job_ends_at_the_deadline(tmp_path):
     assert not ok and "not finished" in why and time.time() - t0 < 60
 
 
+def test_side_measurements_and_the_output_dump_are_opt_in(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
 def test_gpus_n_without_a_job_environment_becomes_the_launcher():
     """No GPU here: the ranks the launcher starts exit with bench.py's own "needs a GPU" message, the launcher reports the
     failing rank and exits non-zero -- instead of the old SystemExit that told the caller to use torch.distributed.run."""

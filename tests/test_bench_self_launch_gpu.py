@@ -1,4 +1,5 @@
-"""GPU: `python bench.py --gpus 2 ...` -- the plain command the driver runs -- launches its own ranks.
+"""GPU: `python bench.py --gpus 2 ... --full` -- the command the driver runs, with its side measurements -- launches its own
+ranks.
 
 Rehearsal on the one GPU of the box: SGL_MI355_SHARE_GPU=1 puts both ranks on device 0 and lets gloo carry the process
 group (RCCL refuses two ranks on one device); the P2P all-reduce kernel over IPC buffers is the data plane, as it would be
@@ -21,7 +22,7 @@ def test_plain_command_at_two_ranks_prints_one_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SGL_MI355_SHARE_GPU="1", SGL_MI355_BENCH_LAUNCH_TIMEOUT="800")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--layers", "2", "--steps", "4",
-                        "--warmup", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
+                        "--warmup", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1,15 +1,18 @@
 # HBM traffic of the decode attention kernel INSIDE the bench step (separate --pmc passes, kernel-trace only), plus the
-# kernel stats and the layer breakdown of the same command.  Output: gpurun_out/r04_decode_pmc_instep.json etc.
+# kernel stats and the layer breakdown of the same command.  Output: $OUT/r04_decode_pmc_instep.json etc. (OUT: any scratch directory)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs"
-rm -rf gpurun_out/pmc_r4
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_r4/fetch -- python3 $ARGS > gpurun_out/pmc_r4_fetch.log 2>&1 &&
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_r4/write -- python3 $ARGS > gpurun_out/pmc_r4_write.log 2>&1 &&
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc_r4/stats -- python3 bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-other-configs > gpurun_out/pmc_r4_stats.log 2>&1
+export OUT=${OUT:-prof_out}
+mkdir -p $OUT
+ARGS="bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-other-configs"
+rm -rf $OUT/pmc_r4
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_r4/fetch -- python3 $ARGS > $OUT/pmc_r4_fetch.log 2>&1 &&
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_r4/write -- python3 $ARGS > $OUT/pmc_r4_write.log 2>&1 &&
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/pmc_r4/stats -- python3 bench.py --steps 16 --warmup 2 --full --no-cpu-baseline --no-other-configs > $OUT/pmc_r4_stats.log 2>&1
 python3 - <<'PY'
-import csv, glob, json
+import csv, glob, json, os
+OUT = os.environ["OUT"]
 def per_launch(counter, d):
-    f = glob.glob(f"gpurun_out/pmc_r4/{d}/*/*counter_collection.csv")[0]
+    f = glob.glob(f"{OUT}/pmc_r4/{d}/*/*counter_collection.csv")[0]
     vals = [float(r["Counter_Value"]) for r in csv.DictReader(open(f))
             if r["Counter_Name"] == counter and "decode_mfma_pair" in r["Kernel_Name"]]
     return vals
@@ -28,22 +31,23 @@ out = {"kernel": "decode_mfma_pair_kernel inside bench.py's decode step (graph r
        "algorithmic_bytes_per_launch_ctx2048": lo, "algorithmic_bytes_per_launch_ctx2072": hi,
        "traffic_over_algorithmic": round(hbm / ((lo + hi) / 2), 4),
        "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over `python3 bench.py --steps 8 --warmup 2 "
-                 "--no-cpu-baseline --no-other-configs`; FETCH_SIZE x 2 (gfx950: 128-B units reported as 64-B) + WRITE_SIZE, KB"}
-json.dump(out, open("gpurun_out/r04_decode_pmc_instep.json", "w"), indent=1)
+                 "--full --no-cpu-baseline --no-other-configs`; FETCH_SIZE x 2 (gfx950: 128-B units reported as 64-B) + WRITE_SIZE, KB"}
+json.dump(out, open(f"{OUT}/r04_decode_pmc_instep.json", "w"), indent=1)
 print(json.dumps(out))
 PY
-cp gpurun_out/pmc_r4/stats/*/*kernel_stats.csv gpurun_out/r04_bench_tp1_kernel_stats.csv 2>/dev/null
-rocprofv3 --kernel-trace --output-format csv -d gpurun_out/pmc_r4/trace -- python3 bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-other-configs > gpurun_out/pmc_r4_trace.log 2>&1
-python3 tools/layer_breakdown.py gpurun_out/pmc_r4/trace/*/*kernel_trace.csv > gpurun_out/r04_layer_breakdown_decode.txt 2>&1
-cat gpurun_out/r04_layer_breakdown_decode.txt
-python3 tools/layer_breakdown.py gpurun_out/pmc_r4/trace/*/*kernel_trace.csv "extend_mfma_kernel<0, 128, int, 2, false, false, 2" fp8_gemm_tiled3 > gpurun_out/r04_layer_breakdown_prefill.txt 2>&1
-cat gpurun_out/r04_layer_breakdown_prefill.txt
+cp $OUT/pmc_r4/stats/*/*kernel_stats.csv $OUT/r04_bench_tp1_kernel_stats.csv 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d $OUT/pmc_r4/trace -- python3 bench.py --steps 16 --warmup 2 --full --no-cpu-baseline --no-other-configs > $OUT/pmc_r4_trace.log 2>&1
+python3 tools/layer_breakdown.py $OUT/pmc_r4/trace/*/*kernel_trace.csv > $OUT/r04_layer_breakdown_decode.txt 2>&1
+cat $OUT/r04_layer_breakdown_decode.txt
+python3 tools/layer_breakdown.py $OUT/pmc_r4/trace/*/*kernel_trace.csv "extend_mfma_kernel<0, 128, int, 2, false, false, 2" fp8_gemm_tiled3 > $OUT/r04_layer_breakdown_prefill.txt 2>&1
+cat $OUT/r04_layer_breakdown_prefill.txt
 # the per-launch counter rows of the decode attention kernel (small), then drop the raw traces (tens of MB)
 python3 - <<'PY'
-import csv, glob
+import csv, glob, os
+OUT = os.environ["OUT"]
 for counter, d in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
-    f = glob.glob(f"gpurun_out/pmc_r4/{d}/*/*counter_collection.csv")[0]
-    with open(f"gpurun_out/r04_decode_pmc_instep_{counter}.csv", "w", newline="") as out:
+    f = glob.glob(f"{OUT}/pmc_r4/{d}/*/*counter_collection.csv")[0]
+    with open(f"{OUT}/r04_decode_pmc_instep_{counter}.csv", "w", newline="") as out:
         w = csv.writer(out)
         w.writerow(["Dispatch_Id", "Kernel", "Grid_Size", "Counter_Name", "Counter_Value"])
         for r in csv.DictReader(open(f)):
@@ -52,6 +56,6 @@ for counter, d in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
 PY
 # (round 5, ADVICE r4: this breakdown used to run AFTER the traces were deleted and wrote only an error; the round-5 profile
 #  set is tools/exp/prof_bench_r05.sh, which takes every breakdown before it drops the traces)
-python3 tools/layer_breakdown.py gpurun_out/pmc_r4/trace/*/*kernel_trace.csv "extend_mfma_kernel<0, 128, int, 2, false, false, 2" "fp8_gemm_wstream_kernel<0, 8" > gpurun_out/r04_layer_breakdown_prefill_128.txt 2>&1
-cat gpurun_out/r04_layer_breakdown_prefill_128.txt
-rm -rf gpurun_out/pmc_r4
+python3 tools/layer_breakdown.py $OUT/pmc_r4/trace/*/*kernel_trace.csv "extend_mfma_kernel<0, 128, int, 2, false, false, 2" "fp8_gemm_wstream_kernel<0, 8" > $OUT/r04_layer_breakdown_prefill_128.txt 2>&1
+cat $OUT/r04_layer_breakdown_prefill_128.txt
+rm -rf $OUT/pmc_r4

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 source tools/gpu_steps.sh
 step r05_final_pytest 900 python -m pytest tests -m gpu -q -p no:cacheprovider
 tail -3 gpurun_out/r05_final_pytest.log
-step r05_bench_tp1 600 python bench.py --steps 20 --warmup 5
+step r05_bench_tp1 600 python bench.py --steps 20 --warmup 5 --full
 tail -c 300 gpurun_out/r05_bench_tp1.log
 step r05_prof_bench 900 bash tools/exp/prof_bench_r05.sh
 grep -A18 "^== " gpurun_out/r05_prof_bench.log | head -60

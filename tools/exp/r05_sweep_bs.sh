@@ -1,8 +1,8 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 source tools/gpu_steps.sh
 for b in 1 8 32 48 128; do
-  step r05_sw_on_$b 300 python bench.py --batch $b --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline
-  SGL_MI355_NO_DEFERRED_EPILOGUE=1 step r05_sw_off_$b 300 python bench.py --batch $b --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline
+  step r05_sw_on_$b 300 python bench.py --batch $b --steps 20 --warmup 5 --full --no-other-configs --no-cpu-baseline
+  SGL_MI355_NO_DEFERRED_EPILOGUE=1 step r05_sw_off_$b 300 python bench.py --batch $b --steps 20 --warmup 5 --full --no-other-configs --no-cpu-baseline
 done
 python - <<'PY'
 import json

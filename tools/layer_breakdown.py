@@ -2,9 +2,9 @@
 """Per-kernel spans of ONE decoder layer from a rocprofv3 --kernel-trace CSV of bench.py (graph replay: a kernel's span runs
 to the next kernel's start; its own duration is End - Start).
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof -- python3 bench.py --steps 16 --warmup 2 \
-        --no-cpu-baseline --no-other-configs
-    python tools/layer_breakdown.py gpurun_out/prof/*/*kernel_trace.csv [anchor-substring [must-contain-substring]]
+    rocprofv3 --kernel-trace --output-format csv -d prof_out/prof -- python3 bench.py --steps 16 --warmup 2 \
+        --full --no-cpu-baseline --no-other-configs        (--full: the prefill passes are side measurements of the bench)
+    python tools/layer_breakdown.py prof_out/prof/*/*kernel_trace.csv [anchor-substring [must-contain-substring]]
 
 A layer = the kernels from one launch of the anchor kernel (default: the decode attention kernel) to the next one; the
 median layer (by total span) of all complete layers in the trace is printed.  must-contain: only layers in which some kernel's
