@@ -34,7 +34,7 @@ extern "C" {
 #define SGL_MI355_ERR_RUNTIME 3          /* a HIP runtime call failed                */
 
 /* ABI version of this header; bumped on any signature change. */
-#define SGL_MI355_ABI_VERSION 14
+#define SGL_MI355_ABI_VERSION 15
 int sgl_mi355_abi_version(void);
 
 /* Copies the calling thread's last error message (NUL-terminated) into buf. Returns its length. */
@@ -442,8 +442,9 @@ int sgl_mi355_awq_gemm(const void* x, const int32_t* qweight, const void* scales
  * SGL_MI355_ERR_UNSUPPORTED without launching and the callers make the separate calls. */
 int sgl_mi355_has_optin_fusions(void);
 
-/* Test aid: the kernel family the last sgl_mi355_fp8_scaled_mm* call of the calling thread launched ("skinny", "oneshot",
- * "astat", "astat_direct", "wstream", "wstream_slab", "tiled", "tiled2", "tiled3"; "" before the first call). */
+/* Test aid: the kernel family the last sgl_mi355_fp8_scaled_mm* / sgl_mi355_fp8_blockwise_scaled_mm* call of the calling
+ * thread launched ("skinny", "oneshot", "astat", "astat_direct", "wstream", "wstream_slab", "tiled", "tiled2", "tiled3";
+ * "block_stream", "block_stream_rowmajor", "block_tiled"; "" before the first call). */
 const char* sgl_mi355_fp8_last_kernel(void);
 
 /* Pre-shuffled ("fragment-major") FP8 weights for the decode GEMMs -- MI355X extension.
@@ -701,6 +702,34 @@ int sgl_mi355_per_token_group_quant_fp8(const void* input, void* output_q, float
                                         int64_t hidden_dim, int64_t group_size, int64_t s_stride_token,
                                         int64_t s_stride_group, float eps, float fp8_min, float fp8_max, int scale_ue8m0,
                                         int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Block-scaled FP8 x FP8 GEMM: 128 x 128 weight blocks, 1 x 128 activation groups (csrc/gemm_fp8_block.hip).
+ * Replaces: fp8_blockwise_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b,
+ *                                   ScalarType out_dtype) -> Tensor
+ *           schema sgl-kernel/csrc/common_extension.cc:112-114, checks csrc/gemm/fp8_blockwise_gemm_kernel.cu:345-423,
+ *           reached from Fp8LinearMethod.apply (fp8.py:462-480, fp8_utils.py:287-307) behind per_token_group_quant_fp8.
+ *   out[m,n] = round16( sum over kb of (sum_{k in block kb} a[m,k] b[k,n])_f32 * sa[m,kb] * sb[kb, n/128] )
+ *   fp32 accumulation within and across blocks, one rounding; with a bias (MI355X extension, what fp8_utils.py:305-306
+ *   adds afterwards): round16(f32(round16(acc)) + f32(bias[n])), two roundings as there.
+ *   mat_a [M,K] e4m3fn row-major (a_stride_m bytes between rows); mat_b [K,N] e4m3fn with stride(0) == 1, passed as its
+ *   storage W[N][K] (b_stride_n bytes between columns), or -- _wshuffled -- in the fragment-major layout of
+ *   sgl_mi355_fp8_shuffle_weight (K % 512 == 0); scales_a fp32, element (m, kb) at m * sa_stride_m + kb * sa_stride_k
+ *   (row-major [M, K/128] and the reference's M-major form alike); scales_b fp32, element (kb, nb) at
+ *   kb * sb_stride_k + nb * sb_stride_n, nb < ceil(N / 128) (the last column may cover a partial block); bias [N] in the
+ *   out dtype or NULL; out [M,N] contiguous bf16/fp16.  K % 128 == 0, N % 16 == 0, any M >= 0.
+ *   M <= 64 runs the weight streamer, split over sgl_mi355_fp8_blockwise_split_k(M, K) = ceil(K / 1024) K slices; with
+ *   more than one slice `workspace` (fp32, caller-owned) must hold slices * M * N floats.  Larger M runs 128 x 128 tiles.
+ *   A violated condition returns SGL_MI355_ERR_INVALID_ARGUMENT with a message naming it; nothing is launched then. */
+int sgl_mi355_fp8_blockwise_scaled_mm(
+    const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b, const void* bias, void* out,
+    float* workspace, int64_t workspace_floats, int64_t M, int64_t N, int64_t K, int64_t a_stride_m, int64_t b_stride_n,
+    int64_t sa_stride_m, int64_t sa_stride_k, int64_t sb_stride_k, int64_t sb_stride_n, int out_dtype, void* stream);
+int sgl_mi355_fp8_blockwise_scaled_mm_wshuffled(
+    const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b, const void* bias, void* out,
+    float* workspace, int64_t workspace_floats, int64_t M, int64_t N, int64_t K, int64_t a_stride_m, int64_t sa_stride_m,
+    int64_t sa_stride_k, int64_t sb_stride_k, int64_t sb_stride_n, int out_dtype, void* stream);
+int64_t sgl_mi355_fp8_blockwise_split_k(int64_t M, int64_t K);
 
 /* Replaces: sgl_per_tensor_quant_fp8(Tensor input, Tensor output_q, Tensor output_s, bool is_static) -> ()
  *           -- common_extension.cc:126-127, csrc/gemm/per_tensor_quant_fp8.cu:9-120; wrapper gemm.py:129-137.

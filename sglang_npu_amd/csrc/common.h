@@ -25,6 +25,9 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 int check_hip(hipError_t e, const char* what);
 
+// What sgl_mi355_fp8_last_kernel() reports (gemm_fp8.hip owns the thread-local; gemm_fp8_block.hip names its kernels too).
+void set_fp8_last_kernel(const char* name);
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;

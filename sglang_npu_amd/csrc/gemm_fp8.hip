@@ -2406,6 +2406,9 @@ __global__ __launch_bounds__(256) void fp8_shuffle_weight_kernel(const uint8_t* 
 }
 
 }  // namespace
+
+void set_fp8_last_kernel(const char* name) { g_last_kernel = name; }
+
 }  // namespace sglm
 
 using namespace sglm;

@@ -24,6 +24,11 @@ from .deferred import DeferredEpilogue
 from .quantization import QuantizationConfig, UnquantizedLinearMethod
 
 
+def _is_block_scale(param) -> bool:
+    """``isinstance(param, BlockQuantScaleParameter)`` of the reference loaders, for SGLang's class and the local one."""
+    return any(c.__name__ == "BlockQuantScaleParameter" for c in type(param).__mro__)
+
+
 class LinearBase(torch.nn.Module):
     # hand-over switches of deferred.py, read on every apply(): class-level defaults so that the lookups never fall through to
     # nn.Module.__getattr__ (a raised AttributeError per miss, ~1 us each, seven per decoder layer in an eager pass)
@@ -76,9 +81,12 @@ class ColumnParallelLinear(LinearBase):
                 self.weight_loader(param, loaded_weight.narrow(param.output_dim, lo, n), i)
                 off += size
             return
+        shard_offset, shard_size = sum(self.output_sizes[:loaded_shard_id]), self.output_sizes[loaded_shard_id]
+        if _is_block_scale(param):  # one scale per block_n output rows: offsets and sizes in blocks (:702-712)
+            block_n = self.quant_method.quant_config.weight_block_size[0]
+            shard_offset, shard_size = -(-shard_offset // block_n), -(-shard_size // block_n)
         param.load_merged_column_weight(loaded_weight, shard_id=loaded_shard_id,
-                                        shard_offset=sum(self.output_sizes[:loaded_shard_id]) // self.tp_size,
-                                        shard_size=self.output_sizes[loaded_shard_id] // self.tp_size,
+                                        shard_offset=shard_offset // self.tp_size, shard_size=shard_size // self.tp_size,
                                         tp_rank=self.tp_rank, tp_size=self.tp_size)
 
     def forward(self, x):
@@ -164,9 +172,12 @@ class QKVParallelLinear(ColumnParallelLinear):
         assert loaded_shard_id in ("q", "k", "v")
         q_size, kv_size = self.num_heads * self.head_size, self.num_kv_heads * self.head_size
         offset = {"q": 0, "k": q_size, "v": q_size + kv_size}[loaded_shard_id]
+        size = q_size if loaded_shard_id == "q" else kv_size
+        if _is_block_scale(param):  # (:899-903)
+            block_n = self.quant_method.quant_config.weight_block_size[0]
+            offset, size = -(-offset // block_n), -(-size // block_n)
         param.load_qkv_weight(loaded_weight, num_heads=self.num_kv_head_replicas, shard_id=loaded_shard_id,
-                              shard_offset=offset, shard_size=q_size if loaded_shard_id == "q" else kv_size,
-                              tp_rank=self.tp_rank)
+                              shard_offset=offset, shard_size=size, tp_rank=self.tp_rank)
 
 
 class RowParallelLinear(LinearBase):

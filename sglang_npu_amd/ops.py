@@ -716,7 +716,8 @@ def has_optin_fusions() -> bool:
 
 
 def fp8_last_kernel() -> str:
-    """Kernel family launched by this thread's last fp8_scaled_mm / fp8_scaled_mm_partials call (test aid)."""
+    """Kernel family launched by this thread's last fp8_scaled_mm / fp8_scaled_mm_partials / fp8_blockwise_scaled_mm call
+    (test aid)."""
     f = _lib.lib().sgl_mi355_fp8_last_kernel
     f.restype = ctypes.c_char_p
     return f().decode()
@@ -811,6 +812,79 @@ def fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> tor
         _ptr(ws), _I64(ws.numel() if ws is not None else 0),
         _I64(M), _I64(N), _I64(K), _I64(mat_a.stride(0) if M > 1 else K), _I64(b_stride_n),
         _I(0 if out_dtype == torch.bfloat16 else 1), _stream(mat_a)))
+    return out
+
+
+def fp8_blockwise_split_k(M: int, K: int) -> int:
+    """K slices fp8_blockwise_scaled_mm runs an [M, K] activation in (the weight streamer's rule, gemm_fp8_block.hip:
+    ceil(K / 1024) up to 64 rows, 1 above)."""
+    f = _lib.lib().sgl_mi355_fp8_blockwise_split_k
+    f.restype = ctypes.c_int64
+    return int(f(_I64(M), _I64(K)))
+
+
+def fp8_blockwise_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> torch.Tensor:
+    """sgl_kernel.fp8_blockwise_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype)
+    -- sgl-kernel/python/sgl_kernel/gemm.py, fp8_blockwise_gemm_kernel.cu:345-423 (same checks, same messages):
+    out = sum over 128-k blocks of (a_blk @ b_blk)_f32 * scales_a[m, kb] * scales_b[kb, n / 128], one rounding.
+    mat_b: the reference's column-major float8_e4m3fn [K, N], or the fragment-major uint8 tensor of fp8_shuffle_weight.
+    scales_a [M, K/128] and scales_b [K/128, ceil(N/128)] fp32 in any strides (the reference's M-major / K-major forms
+    and the row-major ones).  bias (this backend's extension): added to the rounded output and rounded again, what
+    fp8_utils.py:305-306 does after the op."""
+    _need_gpu(mat_a, mat_b, scales_a, scales_b, bias)
+    if mat_a.dim() != 2:
+        raise RuntimeError("mat_a must be a 2D tensor")
+    if mat_a.stride(1) != 1:
+        raise RuntimeError("mat_a must be a row major tensor")
+    if mat_b.dtype == torch.uint8:
+        K, N = fp8_weight_kn(mat_b)  # raises unless it is the fragment-major tensor
+        shuf, b_stride_n = True, K
+        if mat_a.size(1) != K:
+            raise RuntimeError("mat_a and mat_b shapes cannot be multiplied")
+    else:
+        if mat_b.dim() != 2:
+            raise RuntimeError("mat_b must be a 2D tensor")
+        if mat_b.stride(0) != 1:
+            raise RuntimeError("mat_a must be a column major tensor")  # (sic: fp8_blockwise_gemm_kernel.cu:356)
+        if mat_a.size(1) != mat_b.size(0):
+            raise RuntimeError("mat_a and mat_b shapes cannot be multiplied")
+        if mat_b.size(0) % 16 != 0:
+            raise RuntimeError("mat_b must be multiple of 16 bytes for memory alignment")
+        if mat_b.dtype != torch.float8_e4m3fn:
+            raise RuntimeError("mat_b must be Float8_e4m3fn")
+        K, N = mat_b.shape
+        shuf, b_stride_n = False, (mat_b.stride(1) if N > 1 else K)
+    if mat_a.size(1) % 16 != 0:
+        raise RuntimeError("mat_a must be multiple of 16 bytes for memory alignment")
+    if mat_a.dtype != torch.float8_e4m3fn:
+        raise RuntimeError("mat_a must be Float8_e4m3fn")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("out_dtype must be Half or BFloat16")
+    M = mat_a.size(0)
+    if scales_a.dim() != 2 or scales_a.size(0) != M or scales_a.size(1) != K // 128:
+        raise RuntimeError("size of scales_a is not matched")
+    if scales_b.dim() != 2 or scales_b.size(0) != K // 128 or scales_b.size(1) != -(-N // 128):
+        raise RuntimeError("size of scales_b is not matched")
+    if scales_a.dtype != torch.float32:
+        raise RuntimeError("scales_a must be Float32")
+    if scales_b.dtype != torch.float32:
+        raise RuntimeError("scales_b must be Float32")
+    if (N * 2) % 16 != 0:
+        raise RuntimeError("out must be multiple of 16 bytes for memory alignment")
+    if bias is not None:
+        if bias.numel() != N or not bias.is_contiguous() or bias.dtype != out_dtype:
+            raise RuntimeError("bias must be contiguous [N] in the output dtype")
+    out = torch.empty((M, N), dtype=out_dtype, device=mat_a.device)
+    slices = fp8_blockwise_split_k(M, K)
+    ws = _fp8_workspace.get(mat_a.device, slices * M * N) if slices > 1 else None
+    common = (_ptr(mat_a), _ptr(mat_b), _ptr(scales_a), _ptr(scales_b), _ptr(bias), _ptr(out), _ptr(ws),
+              _I64(ws.numel() if ws is not None else 0), _I64(M), _I64(N), _I64(K), _I64(mat_a.stride(0) if M > 1 else K))
+    strides = (_I64(scales_a.stride(0)), _I64(scales_a.stride(1)), _I64(scales_b.stride(0)), _I64(scales_b.stride(1)),
+               _I(0 if out_dtype == torch.bfloat16 else 1), _stream(mat_a))
+    if shuf:
+        _lib.check(_lib.lib().sgl_mi355_fp8_blockwise_scaled_mm_wshuffled(*common, *strides))
+    else:
+        _lib.check(_lib.lib().sgl_mi355_fp8_blockwise_scaled_mm(*common, _I64(b_stride_n), *strides))
     return out
 
 

@@ -130,6 +130,11 @@ class ChannelQuantScaleParameter(_ColumnvLLMParameter):
     """Per-output-channel scales (parameter.py:290-296)."""
 
 
+class BlockQuantScaleParameter(_ColumnvLLMParameter, RowvLLMParameter):
+    """Scales of block-quantised weights, one per block_n x block_k block (parameter.py:299-305): column- and
+    row-shardable; the layers hand it shard offsets and sizes in BLOCK units (linear.py:702-710, 899-903)."""
+
+
 class PackedvLLMParameter(ModelWeightParameter):
     """Weights packed several to a word along ``packed_dim`` (parameter.py:416-458): shard offsets and
     sizes given in logical columns are divided by ``packed_factor`` before slicing."""
@@ -208,7 +213,8 @@ def write_epoch(p: torch.Tensor):
 _LOCAL = SimpleNamespace(
     BasevLLMParameter=BasevLLMParameter, _ColumnvLLMParameter=_ColumnvLLMParameter, RowvLLMParameter=RowvLLMParameter,
     ModelWeightParameter=ModelWeightParameter, GroupQuantScaleParameter=GroupQuantScaleParameter,
-    ChannelQuantScaleParameter=ChannelQuantScaleParameter, PackedvLLMParameter=PackedvLLMParameter, source="local")
+    ChannelQuantScaleParameter=ChannelQuantScaleParameter, BlockQuantScaleParameter=BlockQuantScaleParameter,
+    PackedvLLMParameter=PackedvLLMParameter, source="local")
 _cached = None
 
 
@@ -224,7 +230,7 @@ def classes(refresh: bool = False):
             BasevLLMParameter=m.BasevLLMParameter, _ColumnvLLMParameter=m._ColumnvLLMParameter,
             RowvLLMParameter=m.RowvLLMParameter, ModelWeightParameter=m.ModelWeightParameter,
             GroupQuantScaleParameter=m.GroupQuantScaleParameter, ChannelQuantScaleParameter=m.ChannelQuantScaleParameter,
-            PackedvLLMParameter=m.PackedvLLMParameter, source="sglang")
+            BlockQuantScaleParameter=m.BlockQuantScaleParameter, PackedvLLMParameter=m.PackedvLLMParameter, source="sglang")
     except Exception:  # SGLang absent or not importable in this process: same-named local classes
         _cached = _LOCAL
     return _cached

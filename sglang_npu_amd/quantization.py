@@ -3,6 +3,7 @@
 Interface mirrored (same method names / argument meaning):
   QuantizationConfig / LinearMethodBase   python/sglang/srt/layers/quantization/base_config.py:15-80,113-203
   W8A8Fp8Config / W8A8Fp8LinearMethod      python/sglang/srt/layers/quantization/w8a8_fp8.py:34-189
+  Fp8Config / Fp8LinearMethod (block FP8)   python/sglang/srt/layers/quantization/fp8.py:110-190, 221-361, 462-480
   apply_fp8_linear                          python/sglang/srt/layers/quantization/fp8_utils.py:510-533,653-704
   AWQConfig / AWQLinearMethod               python/sglang/srt/layers/quantization/awq.py:75-150,319-418
   QUANTIZATION_METHODS registry             python/sglang/srt/layers/quantization/__init__.py:74-121
@@ -380,6 +381,137 @@ class W8A8Fp8LinearMethod(LinearMethodBase):
                                               out_dtype, bias)
 
 
+# ----------------------------------------------------------------------------- FP8, 128 x 128 weight blocks
+ACTIVATION_SCHEMES = ["static", "dynamic"]
+
+
+class Fp8Config(QuantizationConfig):
+    """fp8.py:110-190: ``quant_method: "fp8"`` checkpoints.  Served here: the serialised, block-quantised form
+    (``weight_block_size: [128, 128]``, Qwen3-FP8 / DeepSeek style) with dynamic activation scales."""
+
+    def __init__(self, is_checkpoint_fp8_serialized: bool = False, activation_scheme: str = "dynamic",
+                 ignored_layers: Optional[List[str]] = None, weight_block_size: Optional[List[int]] = None):
+        self.is_checkpoint_fp8_serialized = is_checkpoint_fp8_serialized
+        if activation_scheme not in ACTIVATION_SCHEMES:
+            raise ValueError(f"Unsupported activation scheme {activation_scheme}")
+        self.activation_scheme = activation_scheme
+        self.ignored_layers = ignored_layers or []
+        if weight_block_size is not None:  # fp8.py:127-140
+            if not is_checkpoint_fp8_serialized:
+                raise ValueError("The block-wise quantization only supports fp8-serialized checkpoint for now.")
+            if len(weight_block_size) != 2:
+                raise ValueError("The quantization block size of weight must have 2 dimensions, but got "
+                                 f"{len(weight_block_size)} dimensions.")
+            if activation_scheme != "dynamic":
+                raise ValueError("The block-wise quantization only supports dynamic activation scheme for now, but got "
+                                 f"{activation_scheme} activation scheme.")
+        self.weight_block_size = weight_block_size
+
+    def get_name(self) -> str:
+        return "fp8"
+
+    def get_supported_act_dtypes(self):
+        return [torch.bfloat16, torch.half]
+
+    @classmethod
+    def get_min_capability(cls) -> int:
+        return 80
+
+    @staticmethod
+    def get_config_filenames():
+        return []
+
+    @classmethod
+    def from_config(cls, config):
+        if "quant_method" not in config or "activation_scheme" not in config:
+            raise ValueError("Cannot find quant_method / activation_scheme in the model's quantization config.")
+        return cls(is_checkpoint_fp8_serialized="fp8" in config["quant_method"],
+                   activation_scheme=config["activation_scheme"], ignored_layers=config.get("ignored_layers"),
+                   weight_block_size=config.get("weight_block_size"))
+
+    def get_quant_method(self, layer, prefix: str):
+        if is_linear_layer(layer):  # fp8.py:178-181
+            if any(prefix == name or prefix.startswith(name + ".") for name in self.ignored_layers):
+                return UnquantizedLinearMethod()
+            return Fp8LinearMethod(self)
+        return None
+
+
+class Fp8LinearMethod(LinearMethodBase):
+    """fp8.py:190-480, the branch block-FP8 checkpoints take: ``weight`` [N, K] e4m3fn with one fp32 scale per 128 x 128
+    block (``weight_scale_inv``), activations quantised per token in groups of 128 along K, then
+    ops.fp8_blockwise_scaled_mm (csrc/gemm_fp8_block.hip).  The other branches of the reference's class (per-tensor FP8,
+    16-bit checkpoints quantised after loading, static activation scales) are not built."""
+
+    def __init__(self, quant_config: Fp8Config):
+        self.quant_config = quant_config
+        self.block_quant = quant_config.weight_block_size is not None
+        if quant_config.activation_scheme != "dynamic":
+            raise NotImplementedError("Fp8LinearMethod: the static activation-scale branch (input_scale, fp8.py:318-332) "
+                                      "is not built")
+        if not (self.block_quant and quant_config.is_checkpoint_fp8_serialized):
+            raise NotImplementedError("Fp8LinearMethod: only serialised block-quantised checkpoints (weight_block_size) are "
+                                      "served; the per-tensor FP8 branch (fp8.py:310-316, 363-460) is not built")
+        if list(quant_config.weight_block_size) != [128, 128]:
+            raise NotImplementedError(f"Fp8LinearMethod: weight_block_size {quant_config.weight_block_size} has no kernel; "
+                                      "only [128, 128] is built")
+
+    def create_weights(self, layer, input_size_per_partition, output_partition_sizes, input_size, output_size,
+                       params_dtype, **extra_weight_attrs):
+        P = _param_classes()
+        weight_loader = extra_weight_attrs.get("weight_loader")
+        block_n, block_k = self.quant_config.weight_block_size
+        n = sum(output_partition_sizes)
+        tp_size = getattr(layer, "tp_size", 1)
+        # fp8.py:242-265
+        if tp_size > 1 and input_size // input_size_per_partition == tp_size and input_size_per_partition % block_k != 0:
+            raise ValueError(f"Weight input_size_per_partition = {input_size_per_partition} is not divisible by "
+                             f"weight quantization block_k = {block_k}.")
+        if (tp_size > 1 and output_size // n == tp_size) or len(output_partition_sizes) > 1:
+            for size in output_partition_sizes:
+                if size % block_n != 0:
+                    raise ValueError(f"Weight output_partition_size = {size} is not divisible by weight quantization "
+                                     f"block_n = {block_n}.")
+        layer.logical_widths = output_partition_sizes
+        layer.input_size_per_partition, layer.output_size_per_partition = input_size_per_partition, n
+        layer.orig_dtype = params_dtype
+        layer.register_parameter("weight", P.ModelWeightParameter(
+            data=torch.empty(n, input_size_per_partition, dtype=torch.float8_e4m3fn), input_dim=1, output_dim=0,
+            weight_loader=weight_loader))
+        scale = P.BlockQuantScaleParameter(
+            data=torch.empty(-(-n // block_n), -(-input_size_per_partition // block_k), dtype=torch.float32), input_dim=1,
+            output_dim=0, weight_loader=weight_loader)
+        scale[:] = torch.finfo(torch.float32).min
+        layer.register_parameter("weight_scale_inv", scale)
+        layer.input_scale = None
+
+    def process_weights_after_loading(self, layer) -> None:
+        weight = layer.weight
+        if ops.is_wshuffled(weight) or getattr(layer, "_sgl_mi355_block_fp8_done", False):
+            return  # re-entered (W8A8Fp8LinearMethod: the bytes are already laid out and the storage must not change)
+        w = weight.data
+        n, k = w.shape
+        if PRESHUFFLE_FP8_WEIGHTS and w.is_cuda and ops.fp8_shuffle_supported(n, k):
+            w = ops.fp8_shuffle_weight(w.contiguous())  # fragment-major uint8 [N / 16, 16 K]
+        layer.weight = torch.nn.Parameter(w, requires_grad=False)
+        layer.weight_scale_inv = torch.nn.Parameter(layer.weight_scale_inv.data, requires_grad=False)
+        layer.input_scale = None
+        layer._sgl_mi355_block_fp8_done = True
+
+    def apply(self, layer, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        # fp8_utils.py:287-307: per_token_group_quant_fp8(x, 128), the block-scaled GEMM, then the bias
+        weight = layer.weight
+        x2 = x.reshape(-1, x.shape[-1])
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        k = x2.shape[1]
+        q = torch.empty_like(x2, dtype=torch.float8_e4m3fn)
+        s = torch.empty((x2.shape[0], k // 128), dtype=torch.float32, device=x.device)
+        ops.sgl_per_token_group_quant_fp8(x2, q, s, 128, 1e-10, -448.0, 448.0, False)
+        mat_b = weight if ops.is_wshuffled(weight) else weight.t()
+        out = ops.fp8_blockwise_scaled_mm(q, mat_b, s, layer.weight_scale_inv.t(), x.dtype, bias)
+        return out.view(*x.shape[:-1], out.shape[-1])
+
+
 # ----------------------------------------------------------------------------- AWQ INT4
 class AWQConfig(QuantizationConfig):
     """awq.py:75-150."""
@@ -524,6 +656,7 @@ class AWQLinearMethod(LinearMethodBase):
 
 QUANTIZATION_METHODS = {
     "w8a8_fp8": W8A8Fp8Config,
+    "fp8": Fp8Config,
     "awq": AWQConfig,
 }
 
