@@ -34,7 +34,7 @@ extern "C" {
 #define SGL_MI355_ERR_RUNTIME 3          /* a HIP runtime call failed                */
 
 /* ABI version of this header; bumped on any signature change. */
-#define SGL_MI355_ABI_VERSION 15
+#define SGL_MI355_ABI_VERSION 16
 int sgl_mi355_abi_version(void);
 
 /* Copies the calling thread's last error message (NUL-terminated) into buf. Returns its length. */
@@ -446,6 +446,29 @@ int sgl_mi355_has_optin_fusions(void);
  * thread launched ("skinny", "oneshot", "astat", "astat_direct", "wstream", "wstream_slab", "tiled", "tiled2", "tiled3";
  * "block_stream", "block_stream_rowmajor", "block_tiled"; "" before the first call). */
 const char* sgl_mi355_fp8_last_kernel(void);
+
+/* Which kernel an FP8 GEMM call would launch, and how -- decided on the host, nothing is launched and no pointer is touched,
+ * so it runs on a machine without a GPU.  The rule itself is fp8_plan() of csrc/gemm_fp8_plan.h; the four GEMM entry points
+ * launch exactly what it returns.  Unused fields are 0. */
+#define SGL_MI355_FP8_PLAN_MM 0           /* sgl_mi355_fp8_scaled_mm(_wshuffled)                    */
+#define SGL_MI355_FP8_PLAN_PARTIALS 1     /* sgl_mi355_fp8_scaled_mm_partials(_wshuffled)           */
+#define SGL_MI355_FP8_PLAN_PARTIALS_A16 2 /* sgl_mi355_fp8_scaled_mm_partials_a16 (opt-in fusion)   */
+#define SGL_MI355_FP8_PLAN_SILU_MUL 3     /* sgl_mi355_fp8_scaled_mm_silu_mul_wshuffled             */
+typedef struct {
+  char family[16];                        /* what sgl_mi355_fp8_last_kernel() reports after the call, plus "tiled3_ks2" etc. */
+  /* template selectors: rows / 16 of the decode kernels; streamer phase length; one-shot S; skinny NB; one-shot / skinny WK;
+   * astat_direct EXACT; tiled2 (NSTAGE, RI, WM, WN); tiled3 (WM, CB, KS, SILU, RAWK); tiled SCALED */
+  int32_t mb, ph, s, nb, wk, exact, nstage, ri, wm, wn, cb, ks, silu, rawk, scaled;
+  int32_t grid_x, grid_y, block, lds;     /* launch geometry; lds = dynamic LDS bytes */
+  /* runtime kernel arguments: K slices (= num_slices of the partials forms); phases (streamer) or k-steps (astat) per slice;
+   * consumer waves; column-block groups; GemmArgs raster_gn / k_steps_per_slice; 1 when a finalize launch follows */
+  int32_t sk, per_slice, waves, groups, raster_gn, k_steps_per_slice, finalize;
+} sgl_mi355_fp8_plan;
+/* kind: SGL_MI355_FP8_PLAN_*; strides in bytes as the entry point of that kind takes them (b_stride_n is ignored for a
+ * pre-shuffled weight); has_workspace / workspace_floats: the split-K workspace the call would pass.  The shape must satisfy
+ * that entry point's argument checks.  Returns 0, or SGL_MI355_ERR_UNSUPPORTED with the entry point's own message. */
+int sgl_mi355_fp8_gemm_plan(int kind, int64_t M, int64_t N, int64_t K, int64_t a_stride_m, int64_t b_stride_n, int b_shuffled,
+                            int has_workspace, int64_t workspace_floats, sgl_mi355_fp8_plan* plan);
 
 /* Pre-shuffled ("fragment-major") FP8 weights for the decode GEMMs -- MI355X extension.
  * Replaces: nothing in the dense w8a8 path of the reference (it keeps the checkpoint's row-major [N, K] weight and only

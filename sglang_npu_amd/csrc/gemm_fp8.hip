@@ -30,6 +30,7 @@
 
 #include <type_traits>
 #include "common.h"
+#include "gemm_fp8_plan.h"
 
 namespace sglm {
 namespace {
@@ -38,7 +39,7 @@ constexpr float kFp8Max = 448.0f;
 
 // Which GEMM kernel family the last fp8_scaled_mm(_partials) call of this thread launched (sgl_mi355_fp8_last_kernel):
 // "skinny", "oneshot", "astat", "astat_direct", "wstream", "wstream_slab", "tiled", "tiled2", "tiled3", "tiled3_silu".  A test aid: the
-// dispatch table of run_gemm is long, and tests/test_fp8_gpu.py names a shape that reaches each family.
+// dispatch rule (fp8_plan, gemm_fp8_plan.h) is long, and tests/test_fp8_gpu.py names a shape that reaches each family.
 thread_local const char* g_last_kernel = "";
 
 // ------------------------------------------------------------------------------------------
@@ -525,37 +526,6 @@ __global__ __launch_bounds__(512) void fp8_gemm_oneshot_kernel(GemmArgs p) {
     }
     *reinterpret_cast<typename H::x8*>(reinterpret_cast<T*>(p.out) + (int64_t)m * p.N + nn) = o;
   }
-}
-
-// picks (S, WK) with WK * S == K / 128, S <= 4, WK <= 8; `used` false when the shape does not qualify
-template <int OUT_DTYPE, int MB>
-int launch_oneshot(const GemmArgs& p, hipStream_t s, bool& used) {
-  used = false;
-  if ((p.K & 127) != 0 || (p.N & 7) != 0) return 0;
-  if ((!p.b_shuf && (int64_t)p.N * p.b_sn >= ((int64_t)1 << 32)) || (int64_t)p.M * p.a_sm >= ((int64_t)1 << 32)) return 0;
-  const int steps = p.K >> 7;
-  int S = 0;
-  for (int c = 1; c <= 4; ++c)
-    if (steps % c == 0 && steps / c <= 8) { S = c; break; }
-  if (S == 0) return 0;
-  const int WK = steps / S;
-  const unsigned grid = (unsigned)((p.N + 15) / 16);
-  // M > 32: 167 VGPRs -> one workgroup per CU; a second round of workgroups (N = 6144: 384) costs more than the
-  // pipelined kernel's 32-column tiles (measured 23.0 vs 20.6 us), so only take shapes that fit one round.
-  static const unsigned max_grid4 = [] { const char* e = getenv("SGL_MI355_ONESHOT_MAX_GRID"); return e ? (unsigned)atoi(e) : 256u; }();  // tuning aid
-  // (one k-step per wave is cheap enough for several rounds: K = 1024, N = 8192 -- 512 workgroups -- 8.2 us vs 14.4)
-  if (MB == 4 && grid > max_grid4 && !(S == 1 && grid <= 1024)) return 0;
-  const int lds = WK * MB * 16 * 16 * 4;
-#define OS_GO(S_)                                                                                          \
-  hipLaunchKernelGGL((fp8_gemm_oneshot_kernel<OUT_DTYPE, MB, S_>), dim3(grid), dim3(64 * WK), lds, s, p)
-  if (S == 1) OS_GO(1);
-  else if (S == 2) OS_GO(2);
-  else if (S == 3) OS_GO(3);
-  else OS_GO(4);
-#undef OS_GO
-  g_last_kernel = "oneshot";
-  used = true;
-  return check_hip(hipGetLastError(), "fp8_gemm_oneshot launch");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1104,162 +1074,6 @@ __global__ __launch_bounds__(576) void fp8_gemm_wstream_kernel(GemmArgs p, float
   }
 }
 
-// finalize of the slab variants (defined below)
-template <int OUT_DTYPE>
-__global__ void fp8_gemm_finalize_kernel(GemmArgs p, const float* slabs, int SK);
-
-template <int OUT_DTYPE, int MB, int PH, bool SLAB>
-int launch_wstream_ph(const GemmArgs& p, float* slabs, int SK, int phases_per_slice, int nc, int groups, hipStream_t s,
-                      bool finalize = true) {
-  auto kern = fp8_gemm_wstream_kernel<OUT_DTYPE, MB, PH, SLAB>;
-  constexpr int lds_ab = 2 * PH * 16 * MB * 128;                       // the two A buffers
-  constexpr int lds_ep = 8 * 16 * MB * (SLAB ? 20 * 4 : 24 * 2);        // epilogue patches of up to 8 consumer waves
-  constexpr int lds = lds_ab > lds_ep ? lds_ab : lds_ep;
-  static_assert(lds <= 160 * 1024, "LDS");
-  static int attr_rc = check_hip(
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-      "hipFuncSetAttribute");
-  if (attr_rc) return attr_rc;
-  g_last_kernel = SLAB ? "wstream_slab" : "wstream";
-  hipLaunchKernelGGL(kern, dim3((unsigned)groups, (unsigned)SK), dim3(64 * (nc + 1)), lds, s, p, slabs,
-                     phases_per_slice);
-  int rc = check_hip(hipGetLastError(), "fp8_gemm_wstream launch");
-  if (rc || !SLAB || !finalize) return rc;
-  const int64_t total = (int64_t)p.M * p.N / 8;
-  hipLaunchKernelGGL((fp8_gemm_finalize_kernel<OUT_DTYPE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p,
-                     (const float*)slabs, SK);
-  return check_hip(hipGetLastError(), "fp8_gemm_finalize launch");
-}
-
-// Shapes: K % 128 == 0 and K / 128 a multiple of a phase length PH in {32, 16, 8} (PH * MB <= 32).
-// slabs == nullptr: one workgroup per 8 column blocks over all of K (wide N).  Otherwise K is split into SK
-// slices of whole phases so that ~256 workgroups exist, partials go to fp32 slabs and a finalize kernel applies
-// the reference epilogue (narrow N, long K: down_proj).
-template <int OUT_DTYPE, int MB>
-int launch_wstream(const GemmArgs& p, float* slabs, int64_t slab_floats, hipStream_t s, bool& used,
-                   int* partial_slices = nullptr) {
-  // partial_slices != nullptr: leave the raw fp32 partial sums in `slabs` (any slice count >= 1) and report the
-  // count; the epilogue runs inside the consumer kernel (sgl_mi355_*_from_partials).
-  used = false;
-  if ((p.K & 127) != 0 || (p.N & 7) != 0 || (p.a_sm & 15) != 0) return 0;
-  if (!p.b_shuf && (int64_t)p.N * p.b_sn >= ((int64_t)1 << 32)) return 0;  // per-lane weight offsets are 32-bit
-  const int steps = p.K >> 7;
-  static const int ph_cap = [] { const char* e = getenv("SGL_MI355_WSTREAM_PH"); return e ? atoi(e) : 32; }();  // tuning aid
-  const int nblocks = (p.N + 15) / 16;
-  // Pick (PH, consumer waves, K slices): one workgroup per CU (the A buffers fill most of the LDS) and a CU draws
-  // only ~10 B/clk from HBM, so minimise the k-steps on the busiest CU (+ ~4 steps' worth of barrier per phase).
-  // Without slabs: all of K per workgroup, longest phase (N = 28672: 7 consumers -> exactly 256 workgroups).
-  int PH = 0, nc = 8, SK = 1, pps = 0, best = 1 << 30;
-  // K / 128 not a multiple of 8 (e.g. 3584 = 28 steps): phases of 4 steps, four weight steps in flight
-  // (phases of 2 steps for the split-K form -- 192 workgroups instead of 48 on the TP = 8 qkv shape 4096 x 768 -- were
-  //  tried: one rank's TP = 4 / 8 step 3.07 -> 3.04 / 2.42 -> 2.45 ms, i.e. nothing; those shapes are launch-bound)
-  const int ph_min = MB >= 16 ? 2 : (steps % 8 == 0 && MB <= 4) ? 8 : 4;  // (MB = 8 / 16: 4 / 2 steps are the 64-KiB buffer)
-  for (int ph = 32 / MB; ph >= ph_min; ph >>= 1) {
-    if (ph > ph_cap && ph > 8) continue;
-    if (steps % ph != 0) continue;
-    const int P = steps / ph;
-    for (int c = 8; c >= 4; --c) {
-      const int groups_c = (nblocks + c - 1) / c;
-      int sk = 1, pp = P;
-      if (slabs != nullptr) {
-        int sk_max = 256 / groups_c;
-        if (sk_max < 1) sk_max = 1;
-        if (sk_max > P) sk_max = P;
-        pp = (P + sk_max - 1) / sk_max;
-        sk = (P + pp - 1) / pp;
-      }
-      const int rounds = (groups_c * sk + 255) / 256;
-      const int cost = rounds * c * pp * (ph + (MB >= 16 ? 1 : 4));  // (a barrier per two steps is the only form at 256 rows)
-      if (cost < best) { best = cost; PH = ph; nc = c; SK = sk; pps = pp; }
-    }
-    if (slabs == nullptr) break;  // the longest phase that divides K
-  }
-  {  // tuning aid: SGL_MI355_WSTREAM_FORCE="PH,nc" for the unsplit (no-slab) form
-    static const char* force = getenv("SGL_MI355_WSTREAM_FORCE");
-    int fph = 0, fnc = 0;
-    if (force && slabs == nullptr && sscanf(force, "%d,%d", &fph, &fnc) == 2 && (fph == 4 || fph == 8 || fph == 16 || fph == 32) &&
-        fph * MB <= 32 && steps % fph == 0 && fnc >= 1 && fnc <= 8) {
-      PH = fph;
-      nc = fnc;
-      SK = 1;
-      pps = steps / fph;
-    }
-  }
-  {  // tuning aid: SGL_MI355_WSTREAM_SLAB_FORCE="PH,nc,SK" for the split-K (slab) form
-    static const char* sforce = getenv("SGL_MI355_WSTREAM_SLAB_FORCE");
-    int fph = 0, fnc = 0, fsk = 0;
-    if (sforce && slabs != nullptr && sscanf(sforce, "%d,%d,%d", &fph, &fnc, &fsk) == 3 && (fph == 4 || fph == 8 || fph == 16 || fph == 32) &&
-        fph * MB <= 32 && steps % fph == 0 && fnc >= 1 && fnc <= 8 && fsk >= 1) {
-      const int P = steps / fph;
-      PH = fph;
-      nc = fnc;
-      pps = (P + fsk - 1) / fsk;
-      SK = (P + pps - 1) / pps;
-    }
-  }
-  if (PH == 0) return 0;
-  if (p.a16 != nullptr && (slabs == nullptr || pps != 1)) return 0;  // the a16 fill covers single-phase slices only
-  const int groups = (nblocks + nc - 1) / nc;
-  if (slabs != nullptr && ((SK < 2 && partial_slices == nullptr) || slab_floats < (int64_t)SK * p.M * p.N)) return 0;
-  if (partial_slices != nullptr) *partial_slices = SK;
-  const bool finalize = partial_slices == nullptr;
-  used = true;
-#define WS_GO(PH_)                                                                                         \
-  return slabs ? launch_wstream_ph<OUT_DTYPE, MB, PH_, true>(p, slabs, SK, pps, nc, groups, s, finalize)    \
-               : launch_wstream_ph<OUT_DTYPE, MB, PH_, false>(p, nullptr, 1, pps, nc, groups, s)
-  if constexpr (MB == 1) { if (PH == 32) WS_GO(32); }
-  if constexpr (MB <= 2) { if (PH == 16) WS_GO(16); }
-  if constexpr (MB <= 8) { if (PH == 4) WS_GO(4); }
-  if constexpr (MB <= 4) WS_GO(8);
-  if constexpr (MB == 16) { if (PH == 2) WS_GO(2); }
-  used = false;  // (MB = 8 / 16 have phases of four / two k-steps only)
-  return 0;
-#undef WS_GO
-}
-
-template <int OUT_DTYPE, int MB>
-int launch_astat_direct(const GemmArgs& p, hipStream_t s, bool& used) {
-  using L = AStat<MB>;
-  used = false;
-  const int steps_total = (p.K + 127) >> 7;
-  const int nblocks = (p.N + 15) / 16;
-  int max_steps = L::MAX_STEPS & ~7;  // multiple of the prefetch depth
-  int SK = (steps_total + max_steps - 1) / max_steps;
-  int steps_per_slice = (((steps_total + SK - 1) / SK) + 7) & ~7;
-  if (steps_per_slice > max_steps) return 0;
-  SK = (steps_total + steps_per_slice - 1) / steps_per_slice;
-  if ((int64_t)p.N * p.b_sn >= ((int64_t)1 << 32)) return 0;  // per-lane weight offsets are 32-bit
-  const int ns_last = steps_total - (SK - 1) * steps_per_slice;
-  const bool exact = (p.K & 127) == 0 && (ns_last & 7) == 0;
-  auto kern = exact ? fp8_gemm_astat_direct_kernel<OUT_DTYPE, MB, true> : fp8_gemm_astat_direct_kernel<OUT_DTYPE, MB, false>;
-  static int attr_rc = [] {
-    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(fp8_gemm_astat_direct_kernel<OUT_DTYPE, MB, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                       "hipFuncSetAttribute");
-    if (rc) return rc;
-    return check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(fp8_gemm_astat_direct_kernel<OUT_DTYPE, MB, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                     "hipFuncSetAttribute");
-  }();
-  if (attr_rc) return attr_rc;
-  int lds = steps_per_slice * L::STEP_BYTES;
-  const int ep_bytes = 8 * L::ROWS * 24 * 2;
-  if (lds < ep_bytes) lds = ep_bytes;
-  // waves per workgroup: one workgroup per CU (the A image fills the LDS), so pick the count that leaves
-  // the fewest column blocks on the busiest CU (N = 28672: 7 waves -> 256 workgroups, 8 -> only 224).
-  // (measured at N = 28672: M = 16 28.0 us with 7 waves vs 29.0 with 8; M = 64 prefers 8 waves: 39.9 vs 42.3)
-  int nw = 8, best = 1 << 30;
-  for (int c = 8; c >= (MB == 4 ? 8 : 4); --c) {
-    const int blocks = (nblocks + c - 1) / c;
-    const int cost = ((blocks + 255) / 256) * c;
-    if (cost < best) { best = cost; nw = c; }
-  }
-  g_last_kernel = "astat_direct";
-  hipLaunchKernelGGL(kern, dim3((unsigned)((nblocks + nw - 1) / nw)), dim3(64 * nw), lds, s, p, SK, steps_per_slice);
-  used = true;
-  return check_hip(hipGetLastError(), "fp8_gemm_astat_direct launch");
-}
-
 // epilogue of the A-stationary kernel: sum the K-slices, then the reference's epilogue
 // (fp8_gemm_kernel.cu:498-546): * w_scale[col], * x_scale[row], + bias, cast.
 template <int OUT_DTYPE>
@@ -1302,45 +1116,6 @@ __global__ __launch_bounds__(256) void fp8_gemm_finalize_kernel(GemmArgs p, cons
     }
     *reinterpret_cast<typename H::x8*>(reinterpret_cast<T*>(p.out) + e) = o;
   }
-}
-
-template <int OUT_DTYPE, int MB>
-int launch_astat(const GemmArgs& p, float* slabs, int64_t slab_floats, hipStream_t s, bool& used) {
-  using L = AStat<MB>;
-  const int steps_total = (p.K + 127) >> 7;
-  const int nblocks = (p.N + 15) / 16;
-  // K-slices: at least enough for the slice of A to fit LDS; more when N is narrow, so that there are
-  // >= ~2048 (column block, slice) items for 256 CUs x 8+ waves -- but never below 4 k-steps per item.
-  int SK = (steps_total + L::MAX_STEPS - 1) / L::MAX_STEPS;
-  const int want = (2048 + nblocks - 1) / nblocks;
-  if (SK < want) SK = want;
-  if (SK > steps_total / 4) SK = steps_total / 4;
-  if (SK < 1) SK = 1;
-  const int steps_per_slice = (steps_total + SK - 1) / SK;
-  SK = (steps_total + steps_per_slice - 1) / steps_per_slice;
-  used = false;
-  if (steps_per_slice > L::MAX_STEPS) return 0;
-  if (slabs == nullptr || slab_floats < (int64_t)SK * p.M * p.N) return 0;
-  int ngroups = 256 / SK;
-  if (ngroups > nblocks) ngroups = nblocks;
-  if (ngroups < 1) ngroups = 1;
-  int nwaves = (nblocks + ngroups - 1) / ngroups;
-  if (nwaves > kAsWaves) nwaves = kAsWaves;
-  auto kern = fp8_gemm_astat_kernel<MB>;
-  const int lds = steps_per_slice * L::STEP_BYTES;
-  static int attr_rc = check_hip(
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-      "hipFuncSetAttribute");
-  if (attr_rc) return attr_rc;
-  g_last_kernel = "astat";
-  hipLaunchKernelGGL(kern, dim3((unsigned)(ngroups * SK)), dim3(64 * nwaves), lds, s, p, slabs, SK, steps_per_slice);
-  int rc = check_hip(hipGetLastError(), "fp8_gemm_astat launch");
-  if (rc) return rc;
-  const int64_t total = (int64_t)p.M * p.N / 8;
-  hipLaunchKernelGGL((fp8_gemm_finalize_kernel<OUT_DTYPE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p,
-                     (const float*)slabs, SK);
-  used = true;
-  return check_hip(hipGetLastError(), "fp8_gemm_finalize launch");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2122,272 +1897,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS, 2) void fp8_gemm_tiled3_kernel(G
 #endif
 }
 
-template <int OUT_DTYPE, int MB, int NB, int WK>
-int launch_skinny(const GemmArgs& p, hipStream_t s) {
-  auto kern = fp8_gemm_skinny_kernel<OUT_DTYPE, MB, NB, WK>;
-  constexpr int lds = WK * MB * 16 * 16 * NB * 4;
-  static int attr_rc = lds <= 65536 ? 0 : check_hip(
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-      "hipFuncSetAttribute");
-  if (attr_rc) return attr_rc;
-  const unsigned grid = (unsigned)((p.N + 16 * NB - 1) / (16 * NB));
-  g_last_kernel = "skinny";
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WK), lds, s, p);
-  return check_hip(hipGetLastError(), "fp8_gemm_skinny launch");
-}
-
-// Tuning override: SGL_MI355_SKINNY="NB,WK" (NB in {1,2,4}, WK in {2,4,8}).
-inline void skinny_override(int& nb, int& wk) {
-  static const char* e = getenv("SGL_MI355_SKINNY");
-  if (e) sscanf(e, "%d,%d", &nb, &wk);
-}
-
-template <int OUT_DTYPE, int MB>
-int dispatch_skinny(const GemmArgs& p, hipStream_t s) {
-  // Wide N: 64-column wave tiles (activation L2 traffic = 1x the weight stream), K split 4 ways.
-  // Narrow N: 32-column tiles and a deeper K split so that enough waves are in flight.
-  int nb = (p.N >= 12288) ? 4 : 2;
-  int wk = (p.N >= 12288) ? 4 : 8;
-  skinny_override(nb, wk);
-#define SK_GO(NB_, WK_) return launch_skinny<OUT_DTYPE, MB, NB_, WK_>(p, s)
-  if (nb == 4) { if (wk == 2) SK_GO(4, 2); if (wk == 8) SK_GO(4, 8); SK_GO(4, 4); }
-  if (nb == 1) { if (wk == 2) SK_GO(1, 2); if (wk == 4) SK_GO(1, 4); SK_GO(1, 8); }
-  if (wk == 2) SK_GO(2, 2);
-  if (wk == 4) SK_GO(2, 4);
-  SK_GO(2, 8);
-#undef SK_GO
-}
-
-template <int OUT_DTYPE>
-int run_gemm(const GemmArgs& p, float* workspace, int64_t workspace_floats, hipStream_t s) {
-  if (p.M <= 64) {
-    static const bool no_astat = getenv("SGL_MI355_NO_ASTAT") != nullptr;  // tuning / A-B aid
-    static const bool no_wstream = getenv("SGL_MI355_NO_WSTREAM") != nullptr;  // tuning / A-B aid
-    static const int direct_min_n = [] { const char* e = getenv("SGL_MI355_WSTREAM_MIN_N"); return e ? atoi(e) : 16 * 8 * 100; }();  // tuning aid
-    // >= ~100 workgroups of 8 column blocks (M = 64, K = 4096: N = 14336 21.6 us here vs 24.1 one-shot; at N = 7168 and
-    // below the two tie or the one-shot kernel wins -- those shapes are latency-, not bandwidth-bound)
-    if (!no_wstream && p.N >= direct_min_n) {
-      bool used = false;
-      int rc = p.M <= 16   ? launch_wstream<OUT_DTYPE, 1>(p, nullptr, 0, s, used)
-               : p.M <= 32 ? launch_wstream<OUT_DTYPE, 2>(p, nullptr, 0, s, used)
-                           : launch_wstream<OUT_DTYPE, 4>(p, nullptr, 0, s, used);
-      if (rc || used) return rc;
-    }
-    if (!no_astat && !p.b_shuf && p.N >= 16 * 8 * 160) {  // same shapes, K tails / odd step counts: phase-filled A image
-      bool used = false;
-      int rc = p.M <= 16   ? launch_astat_direct<OUT_DTYPE, 1>(p, s, used)
-               : p.M <= 32 ? launch_astat_direct<OUT_DTYPE, 2>(p, s, used)
-                           : launch_astat_direct<OUT_DTYPE, 4>(p, s, used);
-      if (rc || used) return rc;
-    }
-    // split-K slabs pay a finalize launch (~4 us): worth it from 40 Mi weights, and from 20 Mi at M > 32 where
-    // the alternative re-reads the activations from L2 per wave (qkv 4096x6144: 12.6 + 4.2 us vs 21.2)
-    static const int slab_env = [] { const char* e = getenv("SGL_MI355_SLAB_MIN_MI"); return e ? atoi(e) : 0; }();  // tuning aid
-    const int steps128 = p.K >> 7;  // the one-shot kernel takes K/128 = WK * S with S <= 4, WK <= 8
-    const bool oneshot_ok = (p.K & 127) == 0 && (steps128 <= 8 || (steps128 <= 32 && (steps128 % 4 == 0 || steps128 % 3 == 0 ||
-                                                                                        (steps128 % 2 == 0 && steps128 <= 16))));
-    const int64_t slab_min = (int64_t)(slab_env ? slab_env : (p.M > 32 ? (oneshot_ok ? 20 : 8) : 40)) << 20;
-    if (!no_wstream && workspace != nullptr && (int64_t)p.N * p.K >= slab_min) {
-      bool used = false;  // narrow N, long K: K split over workgroups, fp32 slabs
-      int rc = p.M <= 16   ? launch_wstream<OUT_DTYPE, 1>(p, workspace, workspace_floats, s, used)
-               : p.M <= 32 ? launch_wstream<OUT_DTYPE, 2>(p, workspace, workspace_floats, s, used)
-                           : launch_wstream<OUT_DTYPE, 4>(p, workspace, workspace_floats, s, used);
-      if (rc || used) return rc;
-    }
-    static const int astat_min = [] { const char* e = getenv("SGL_MI355_ASTAT_MIN_MI"); return e ? atoi(e) : 40; }();  // tuning aid
-    if (!no_astat && !p.b_shuf && workspace != nullptr && (int64_t)p.N * p.K >= ((int64_t)astat_min << 20)) {
-      bool used = false;
-      int rc = p.M <= 16   ? launch_astat<OUT_DTYPE, 1>(p, workspace, workspace_floats, s, used)
-               : p.M <= 32 ? launch_astat<OUT_DTYPE, 2>(p, workspace, workspace_floats, s, used)
-                           : launch_astat<OUT_DTYPE, 4>(p, workspace, workspace_floats, s, used);
-      if (rc || used) return rc;
-    }
-    static const bool no_oneshot = getenv("SGL_MI355_NO_ONESHOT") != nullptr;  // tuning / A-B aid
-    if (!no_oneshot) {
-      bool used = false;
-      int rc = p.M <= 16   ? launch_oneshot<OUT_DTYPE, 1>(p, s, used)
-               : p.M <= 32 ? launch_oneshot<OUT_DTYPE, 2>(p, s, used)
-                           : launch_oneshot<OUT_DTYPE, 4>(p, s, used);
-      if (rc || used) return rc;
-    }
-    if (p.b_shuf) {  // a pre-shuffled weight is only read by the weight-streaming, one-shot and tiled-v2 kernels
-      bool used = false;
-      int rc = p.M <= 16   ? launch_wstream<OUT_DTYPE, 1>(p, nullptr, 0, s, used)
-               : p.M <= 32 ? launch_wstream<OUT_DTYPE, 2>(p, nullptr, 0, s, used)
-                           : launch_wstream<OUT_DTYPE, 4>(p, nullptr, 0, s, used);
-      if (rc || used) return rc;
-      set_error("fp8_scaled_mm (pre-shuffled weight): no kernel for M=%d N=%d K=%d", p.M, p.N, p.K);
-      return SGL_MI355_ERR_UNSUPPORTED;
-    }
-    if (p.M <= 16) return dispatch_skinny<OUT_DTYPE, 1>(p, s);
-    if (p.M <= 32) return dispatch_skinny<OUT_DTYPE, 2>(p, s);
-    return dispatch_skinny<OUT_DTYPE, 4>(p, s);
-  }
-  if (p.M <= 128) {
-    // 65..128 rows (a decode batch of up to 128): still weight-bound, and the tiled kernels below would put these shapes on
-    // N / 128 CUs (down_proj 4096 x 14336 at M = 128: 32 tiles, 64.8 us).  The weight streamer with 128-row A phases (MB = 8,
-    // phases of four k-steps) keeps every CU streaming: direct form for wide N, split-K slabs + finalize otherwise.
-    static const bool no_wstream128 = getenv("SGL_MI355_NO_WSTREAM") != nullptr || getenv("SGL_MI355_NO_WSTREAM_M128") != nullptr;  // A/B aid
-    static const int direct_min_n128 = [] { const char* e = getenv("SGL_MI355_WSTREAM_MIN_N"); return e ? atoi(e) : 16 * 8 * 100; }();
-    if (!no_wstream128 && (p.K & 511) == 0) {
-      bool used = false;
-      if (p.N >= direct_min_n128) {
-        int rc = launch_wstream<OUT_DTYPE, 8>(p, nullptr, 0, s, used);
-        if (rc || used) return rc;
-      }
-      // split-K form from 8 Mi weights.  Eager launch loops, M = 128, us, tiled -> streamer: down_proj (4096 x 14336) 64.8 -> 25.8,
-      // gate_up direct 31.5 -> 30.1, but o_proj (4096 x 4096) 21.3 -> 30.9 and qkv 22.0 -> 23.3; in the graph-replayed model step
-      // (where the finalize launch costs a boundary, not a launch gap) taking all of them is still ahead: Llama-3-8B bs = 128
-      // 11.18 ms tiled -> 10.03 with down / gate_up only -> 9.86 with all four; bs = 96 8.86 -> 8.63 (same box)
-      if (workspace != nullptr && (int64_t)p.N * p.K >= ((int64_t)8 << 20)) {
-        int rc = launch_wstream<OUT_DTYPE, 8>(p, workspace, workspace_floats, s, used);
-        if (rc || used) return rc;
-      }
-    }
-  }
-  if (p.M <= 256) {
-    // 129..256 rows: the same again with a 256-row A image and phases of two k-steps (MB = 16).  Measured: see DESIGN 4.8.9.
-    static const bool no_wstream256 = getenv("SGL_MI355_NO_WSTREAM") != nullptr || getenv("SGL_MI355_NO_WSTREAM_M256") != nullptr;  // A/B aid
-    static const int direct_min_n256 = [] { const char* e = getenv("SGL_MI355_WSTREAM_MIN_N"); return e ? atoi(e) : 16 * 8 * 100; }();
-    // At 256 rows the streamer is MFMA- / LDS-bound itself (64 MFMAs and 32 KB of fragment reads per wave and k-step), so only
-    // the long-K, narrow-N layers gain, where the tiled kernels run on N / 128 CUs (eager loops, M = 256, us, tiled -> streamer:
-    // down_proj 4096 x 14336 64.4 -> 37.7; gate_up 44.9 -> 54.7, qkv 22.4 -> 27.7, o 20.8 -> 25.7 stay tiled).
-    // SGL_MI355_WSTREAM_M256_ALL=1 takes it for every shape (A/B aid).
-    static const bool all256 = getenv("SGL_MI355_WSTREAM_M256_ALL") != nullptr;
-    if (!no_wstream256 && (p.K & 511) == 0) {
-      bool used = false;
-      if (all256 && p.N >= direct_min_n256) {
-        int rc = launch_wstream<OUT_DTYPE, 16>(p, nullptr, 0, s, used);
-        if (rc || used) return rc;
-      }
-      if (workspace != nullptr && (int64_t)p.N * p.K >= ((int64_t)(all256 ? 8 : 40) << 20) && (all256 || p.K >= 2 * p.N)) {
-        int rc = launch_wstream<OUT_DTYPE, 16>(p, workspace, workspace_floats, s, used);
-        if (rc || used) return rc;
-      }
-    }
-  }
-  if (p.b_shuf && (p.K & 127) != 0) {
-    set_error("fp8_scaled_mm (pre-shuffled weight): K must be a multiple of 128");
-    return SGL_MI355_ERR_UNSUPPORTED;
-  }
-  // v2 (LDS-DMA + block-scaled MFMA) whenever K has no tail; variant by tile count (see the kernel's comment).
-  static const int v2_env = [] { const char* e = getenv("SGL_MI355_TILED_V2"); return e ? atoi(e) : -1; }();  // 0 off; 2, 3, 8, 48, 84 force a variant
-  const unsigned grid_s = (unsigned)(((p.M + kTM - 1) / kTM) * ((p.N + kTN - 1) / kTN));
-  // Selection (measured, M = 4096 / 512, PFLOP/s): 256x256 x 8 waves 1.62-2.26 wherever there are enough of the big
-  // tiles (>= 192: three quarters of the CUs) -- e.g. 2.05 vs 1.57 at 4096x4096x4096; 128x128: with at most one tile per
-  // CU three stages and EIGHT waves (32x64 per wave: two waves per SIMD hide each other's latency; M = 1024 o/down
-  // 26.7 / 74.4 us vs 29.0 / 81.9 with four waves), else two stages x two workgroups per CU.
-  // (A 4-wave 256x256 with 128x128 wave tiles -- MFMA-bound on paper -- reached only 1.47-2.12: with one wave per SIMD
-  //  every barrier and first-fragment latency is exposed.)
-  const unsigned grid_b = (unsigned)(((p.M + 255) / 256) * ((p.N + 255) / 256));
-  int v2 = v2_env >= 0 ? v2_env : (grid_b >= 192 ? 84 : (grid_s <= 256 ? 22 : 2));
-  if (p.b_shuf && v2 == 0) v2 = 2;  // the register-staged predecessor below does not read the pre-shuffled layout
-  // v3 (weights global -> VGPR, pre-shuffled weights only) from 192 tiles of 128 x 256 (same box, us, v2 -> v3: M = 1024 qkv
-  // 38.4 -> 36.5, gate_up 116.4 -> 111.6; M = 2048 o 40.6 -> 37.6, down 122.0 -> 100.4; M = 4096 qkv 123.9 -> 93.5, gate_up
-  // 436 -> 396; M = 8192 gate_up 920 -> 774, down 397 -> 358; below that the 128 x 128 v2 tiles fill the chip better).
-  // Column tiles per rasterisation group: 4 (1 / 2 / 4 / 8 / 16 at M = 4096 gate_up: 437 / 418 / 408 / 403 / 435 us).
-  static const int v3_env = [] { const char* e = getenv("SGL_MI355_TILED_V3"); return e ? atoi(e) : -1; }();  // 0 off; 1 / 2 force 256x256x8 waves / 128x256x4 waves (A/B aid)
-  static const int gn_env = [] { const char* e = getenv("SGL_MI355_T3_GN"); return e ? atoi(e) : 0; }();       // tuning aid
-  // 128 x 256 tiles, or 128 x 192 where that leaves less work on the busiest CU: tiles per CU (rounded up) x tile width.  Only
-  // the qkv-like widths gain (4096 -> 6144, same box, 256- vs 192-wide: M = 1024 36.5 -> 33.9 us, 192 -> 256 tiles; M = 2048
-  // 53.0 -> 49.6, 384 -> 512 tiles); wherever the products tie the wider tile wins (M = 4096 93.2 vs 102.4) and forcing the
-  // narrow one elsewhere costs 10-20 % (profiles/r03_prefill_gemm_cb3.txt).  SGL_MI355_T3_CB=3|4 forces one (A/B aid).
-  static const int cb_env = [] { const char* e = getenv("SGL_MI355_T3_CB"); return e ? atoi(e) : 0; }();
-  const unsigned tiles_m3 = (unsigned)((p.M + 127) / 128);
-  const unsigned grid_4 = tiles_m3 * (unsigned)((p.N + 255) / 256), grid_c3 = tiles_m3 * (unsigned)((p.N + 191) / 192);
-  const unsigned cost4 = ((grid_4 + 255) / 256) * 4, cost3 = ((grid_c3 + 255) / 256) * 3;
-  const int cb = (cb_env == 3 || cb_env == 4) ? cb_env : (cost3 < cost4 ? 3 : 4);
-  const unsigned grid_3 = cb == 3 ? grid_c3 : grid_4;
-  if (p.b_shuf && (p.K & 511) == 0 && (v3_env > 0 || (v3_env != 0 && grid_3 >= 192))) {
-#define TILED3_GO(WM_, CB_)                                                                                        \
-  {                                                                                                               \
-    GemmArgs p3 = p;                                                                                              \
-    p3.raster_gn = gn_env > 0 ? gn_env : 4;                                                                       \
-    auto k3 = fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, WM_, 4, CB_>;                                               \
-    constexpr int tmb = 128 * WM_, tnb = 64 * CB_;                                                                \
-    constexpr int lds_st = 3 * tmb * 128, lds_ep = WM_ * 4 * 64 * 72 * 2;                                         \
-    constexpr int lds3 = lds_st > lds_ep ? lds_st : lds_ep;                                                       \
-    static int a3 = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k3),                              \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds3), "hipFuncSetAttribute"); \
-    if (a3) return a3;                                                                                            \
-    const unsigned g3 = (unsigned)(((p.M + tmb - 1) / tmb) * ((p.N + tnb - 1) / tnb));                            \
-    g_last_kernel = "tiled3";                                                                                     \
-    hipLaunchKernelGGL(k3, dim3(g3), dim3(256 * WM_), lds3, s, p3);                                               \
-    return check_hip(hipGetLastError(), "fp8_gemm_tiled3 launch");                                                \
-  }
-    // one tile per CU or fewer (M = 1024 qkv: 256 tiles of 128 x 192): the eight-wave form with two k groups (see the kernel)
-    // SGL_MI355_T3_KS=1|2 forces one (A/B aid)
-    static const int ks_env = [] { const char* e = getenv("SGL_MI355_T3_KS"); return e ? atoi(e) : 0; }();
-    if (v3_env <= 0 && (ks_env == 2 || (ks_env != 1 && grid_3 <= 256))) {
-#define TILED3_KS2(CB_)                                                                                           \
-  {                                                                                                               \
-    GemmArgs p3 = p;                                                                                              \
-    p3.raster_gn = gn_env > 0 ? gn_env : 4;                                                                       \
-    auto k3 = fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, CB_, false, 2>;                                       \
-    constexpr int lds_st = 3 * 2 * 128 * 128, lds_hand = 4 * 8 * CB_ * 4 * 64 * 4;                                \
-    constexpr int lds3 = lds_st > lds_hand ? lds_st : lds_hand;                                                   \
-    static int a3 = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k3),                              \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds3), "hipFuncSetAttribute"); \
-    if (a3) return a3;                                                                                            \
-    const unsigned g3 = (unsigned)(((p.M + 127) / 128) * ((p.N + 64 * CB_ - 1) / (64 * CB_)));                    \
-    g_last_kernel = "tiled3_ks2";                                                                                 \
-    hipLaunchKernelGGL(k3, dim3(g3), dim3(512), lds3, s, p3);                                                     \
-    return check_hip(hipGetLastError(), "fp8_gemm_tiled3 (two k groups) launch");                                 \
-  }
-      if (cb == 3) TILED3_KS2(3)
-      TILED3_KS2(4)
-#undef TILED3_KS2
-    }
-    if (v3_env == 1) TILED3_GO(2, 4)
-    // Round 5: few row tiles x a very wide output (M = 1024 gate_up of Llama-3-8B: 4 x 112 tiles of 256 x 256 = 1.75 rounds of one
-    // eight-wave workgroup per CU) take the 256 x 256 form: 112.0 vs 124.4-126.8 us for the 128 x 256 form's 896 tiles (the same
-    // 1.75 rounds at two per CU, half the operand reuse per byte entering the CU), and ahead of the vendor library's 116.4
-    // (profiles/r05_prefill_gemm_forms.txt).  Everywhere else measured the 256 x 256 form loses (M = 1024 qkv / o / down: 53 / 50 /
-    // 147 us against 33 / 25 / 72; M = 4096 qkv / gate_up / down 108 / 418 / 186 against 92 / 393 / 180), so the rule is narrow.
-    if (v3_env < 0 && (p.M + 255) / 256 <= 4 && grid_b >= 384 && grid_b <= 512) TILED3_GO(2, 4)
-    if (cb == 3) TILED3_GO(1, 3)
-    TILED3_GO(1, 4)
-#undef TILED3_GO
-  }
-  if (v2 && (p.K & 127) == 0) {
-#define TILED2_GO(NST, RI_, WM_, WN_)                                                                             \
-  {                                                                                                               \
-    auto k2 = fp8_gemm_tiled2_kernel<OUT_DTYPE, NST, RI_, WM_, WN_>;                                              \
-    constexpr int tmb = 16 * RI_ * WM_, tnb = 64 * WN_;                                                           \
-    constexpr int lds_st = NST * (tmb + tnb) * 128, lds_ep = WM_ * WN_ * 64 * 72 * 2;                             \
-    constexpr int lds2 = lds_st > lds_ep ? lds_st : lds_ep;                                                       \
-    static int a2 = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k2),                              \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds2), "hipFuncSetAttribute"); \
-    if (a2) return a2;                                                                                            \
-    const unsigned g2 = (unsigned)(((p.M + tmb - 1) / tmb) * ((p.N + tnb - 1) / tnb));                            \
-    g_last_kernel = "tiled2";                                                                                         \
-    hipLaunchKernelGGL(k2, dim3(g2), dim3(64 * WM_ * WN_), lds2, s, p);                                           \
-    return check_hip(hipGetLastError(), "fp8_gemm_tiled2 launch");                                                \
-  }
-    if (v2 == 22) TILED2_GO(3, 2, 4, 2)  // 128x128 with 8 waves (32x64 per wave)
-    if (v2 == 84) TILED2_GO(2, 8, 2, 4)
-    if (v2 == 48) TILED2_GO(3, 4, 4, 2)
-    if (v2 == 8) TILED2_GO(3, 8, 2, 2)
-    if (v2 == 2) TILED2_GO(2, 4, 2, 2)
-    TILED2_GO(3, 4, 2, 2)
-#undef TILED2_GO
-  }
-  static const bool scaled = [] { const char* e = getenv("SGL_MI355_TILED_SCALED"); return e ? atoi(e) != 0 : true; }();  // A-B aid
-  auto kern = scaled ? fp8_gemm_tiled_kernel<OUT_DTYPE, true> : fp8_gemm_tiled_kernel<OUT_DTYPE, false>;
-  constexpr int lds = 2 * kStageBytes;
-  static int attr_rc = [] {
-    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(fp8_gemm_tiled_kernel<OUT_DTYPE, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute");
-    return rc ? rc : check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(fp8_gemm_tiled_kernel<OUT_DTYPE, false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute");
-  }();
-  if (attr_rc) return attr_rc;
-  const unsigned grid = (unsigned)(((p.M + kTM - 1) / kTM) * ((p.N + kTN - 1) / kTN));
-  g_last_kernel = "tiled";
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
-  return check_hip(hipGetLastError(), "fp8_gemm_tiled launch");
-}
-
 // Row-major [N][K] FP8 weight <-> the fragment-major layout the decode kernels stream (GemmArgs::b_shuf).  One thread
 // per 16-byte piece: piece (nb, ks, half, lane = 16 g + r16) <-> bytes 128 ks + 64 half + 16 g .. + 16 of row 16 nb + r16.
 __global__ __launch_bounds__(256) void fp8_shuffle_weight_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -2403,6 +1912,154 @@ __global__ __launch_bounds__(256) void fp8_shuffle_weight_kernel(const uint8_t* 
   const int64_t rm = (nb * 16 + (lane & 15)) * row_stride + ks * 128 + half * 64 + (lane >> 4) * 16;
   if (inverse) *reinterpret_cast<uint4*>(dst + rm) = *reinterpret_cast<const uint4*>(src + piece * 16);
   else *reinterpret_cast<uint4*>(dst + piece * 16) = *reinterpret_cast<const uint4*>(src + rm);
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side of the GEMMs.  WHICH kernel a shape gets, and with what geometry, is decided by fp8_plan() (gemm_fp8_plan.h);
+// launch() only turns the plan into the template instantiation it names.
+static_assert(AStat<1>::STEP_BYTES == astat_step_bytes(1) && AStat<2>::MAX_STEPS == astat_max_steps(2) &&
+                  AStat<4>::MAX_STEPS == astat_max_steps(4) && kAsWaves == kAstatWaves && 2 * kStageBytes == kTiledLds,
+              "gemm_fp8_plan.h repeats these constants of the kernels");
+
+// Raise one kernel instantiation's dynamic-LDS limit to BYTES, once per process (0: the default limit covers it).
+template <auto KERN, int BYTES>
+int lds_limit() {
+  static int rc = BYTES == 0 ? 0 : check_hip(
+      hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES), "hipFuncSetAttribute");
+  return rc;
+}
+
+template <auto KERN, int ATTR_LDS, class... Args>
+int launch_kernel(const char* what, const Fp8Plan& pl, hipStream_t s, Args... args) {
+  if (int rc = lds_limit<KERN, ATTR_LDS>()) return rc;
+  hipLaunchKernelGGL(KERN, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(pl.block), pl.lds, s, args...);
+  return check_hip(hipGetLastError(), what);
+}
+
+int not_built(int selector) {
+  set_error("fp8 gemm: the plan names a kernel form that is not built (selector %d)", selector);
+  return SGL_MI355_ERR_RUNTIME;
+}
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a plan's selector as a template argument
+template <int... Vs, class F>
+int with_const(int v, F&& f) {
+  int rc = -1;
+  ((v == Vs ? (void)(rc = f(std::integral_constant<int, Vs>{})) : (void)0), ...);
+  return rc == -1 ? not_built(v) : rc;
+}
+
+// sum the K slices and apply the reference's epilogue (the slab forms of the streamer and of astat)
+template <int OUT_DTYPE>
+int launch_finalize(const GemmArgs& p, const float* slabs, int SK, hipStream_t s) {
+  const int64_t total = (int64_t)p.M * p.N / 8;
+  hipLaunchKernelGGL((fp8_gemm_finalize_kernel<OUT_DTYPE>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, slabs, SK);
+  return check_hip(hipGetLastError(), "fp8_gemm_finalize launch");
+}
+
+template <int OUT_DTYPE>
+int launch(const Fp8Plan& pl, const GemmArgs& p, float* workspace, hipStream_t s) {
+  if (pl.rc) {
+    set_error("%s", pl.error);
+    return pl.rc;
+  }
+  g_last_kernel = fp8_family_name(pl.fam);
+  GemmArgs p3 = p;  // the tiled3 forms' own arguments
+  p3.raster_gn = pl.raster_gn;
+  int rc = 0;
+  const char* what = "";
+  switch (pl.fam) {
+    case Fp8Family::SKINNY:
+      return with_const<1, 2, 4>(pl.mb, [&](auto mb) {
+        return with_const<1, 2, 4>(pl.nb, [&](auto nb) {
+          return with_const<2, 4, 8>(pl.wk, [&](auto wk) {
+            constexpr int MB = decltype(mb)::value, NB = decltype(nb)::value, WK = decltype(wk)::value, lds = skinny_lds(MB, NB, WK);
+            return launch_kernel<fp8_gemm_skinny_kernel<OUT_DTYPE, MB, NB, WK>, (lds <= 65536 ? 0 : lds)>("fp8_gemm_skinny launch", pl, s, p);
+          });
+        });
+      });
+    case Fp8Family::ONESHOT:
+      return with_const<1, 2, 4>(pl.mb, [&](auto mb) {
+        return with_const<1, 2, 3, 4>(pl.s, [&](auto S) {
+          constexpr auto kern = fp8_gemm_oneshot_kernel<OUT_DTYPE, decltype(mb)::value, decltype(S)::value>;
+          return launch_kernel<kern, 0>("fp8_gemm_oneshot launch", pl, s, p);
+        });
+      });
+    case Fp8Family::ASTAT:
+      rc = with_const<1, 2, 4>(pl.mb, [&](auto mb) {
+        constexpr auto kern = fp8_gemm_astat_kernel<decltype(mb)::value>;
+        return launch_kernel<kern, 160 * 1024>("fp8_gemm_astat launch", pl, s, p, workspace, (int)pl.sk, (int)pl.per_slice);
+      });
+      return rc ? rc : launch_finalize<OUT_DTYPE>(p, workspace, pl.sk, s);
+    case Fp8Family::ASTAT_DIRECT:
+      return with_const<1, 2, 4>(pl.mb, [&](auto mb) {
+        constexpr auto exact = fp8_gemm_astat_direct_kernel<OUT_DTYPE, decltype(mb)::value, true>;
+        constexpr auto ragged = fp8_gemm_astat_direct_kernel<OUT_DTYPE, decltype(mb)::value, false>;
+        if (int rc = lds_limit<exact, 160 * 1024>()) return rc;  // both forms on the first use of either
+        if (int rc = lds_limit<ragged, 160 * 1024>()) return rc;
+        const char* what = "fp8_gemm_astat_direct launch";
+        return pl.exact ? launch_kernel<exact, 0>(what, pl, s, p, (int)pl.sk, (int)pl.per_slice)
+                        : launch_kernel<ragged, 0>(what, pl, s, p, (int)pl.sk, (int)pl.per_slice);
+      });
+    case Fp8Family::WSTREAM:
+    case Fp8Family::WSTREAM_SLAB:
+      rc = with_const<1, 2, 4, 8, 16>(pl.mb, [&](auto mb) {
+        return with_const<2, 4, 8, 16, 32>(pl.ph, [&](auto ph) {
+          constexpr int MB = decltype(mb)::value, PH = decltype(ph)::value;
+          if constexpr (MB == 16 ? PH == 2 : (PH >= 4 && PH * MB <= 32)) {  // the phase lengths each A image is built with
+            constexpr auto slab = fp8_gemm_wstream_kernel<OUT_DTYPE, MB, PH, true>;
+            constexpr auto direct = fp8_gemm_wstream_kernel<OUT_DTYPE, MB, PH, false>;
+            const char* what = "fp8_gemm_wstream launch";
+            return pl.fam == Fp8Family::WSTREAM_SLAB
+                       ? launch_kernel<slab, wstream_lds(MB, PH, true)>(what, pl, s, p, workspace, (int)pl.per_slice)
+                       : launch_kernel<direct, wstream_lds(MB, PH, false)>(what, pl, s, p, (float*)nullptr, (int)pl.per_slice);
+          } else {
+            return not_built(PH);
+          }
+        });
+      });
+      return rc || !pl.finalize ? rc : launch_finalize<OUT_DTYPE>(p, workspace, pl.sk, s);
+    case Fp8Family::TILED:
+      if ((rc = lds_limit<fp8_gemm_tiled_kernel<OUT_DTYPE, true>, kTiledLds>())) return rc;  // both forms on the first use of either
+      if ((rc = lds_limit<fp8_gemm_tiled_kernel<OUT_DTYPE, false>, kTiledLds>())) return rc;
+      return pl.scaled ? launch_kernel<fp8_gemm_tiled_kernel<OUT_DTYPE, true>, 0>("fp8_gemm_tiled launch", pl, s, p)
+                       : launch_kernel<fp8_gemm_tiled_kernel<OUT_DTYPE, false>, 0>("fp8_gemm_tiled launch", pl, s, p);
+    case Fp8Family::TILED2:
+#define TILED2_IS(NST, RI_, WM_, WN_)                                                                                 \
+  if (pl.nstage == NST && pl.ri == RI_ && pl.wm == WM_ && pl.wn == WN_)                                               \
+    return launch_kernel<fp8_gemm_tiled2_kernel<OUT_DTYPE, NST, RI_, WM_, WN_>, tiled2_lds(NST, RI_, WM_, WN_)>(what, pl, s, p);
+      what = "fp8_gemm_tiled2 launch";
+      TILED2_IS(3, 2, 4, 2) TILED2_IS(2, 8, 2, 4) TILED2_IS(3, 4, 4, 2) TILED2_IS(3, 8, 2, 2) TILED2_IS(2, 4, 2, 2) TILED2_IS(3, 4, 2, 2)
+#undef TILED2_IS
+      return not_built(pl.ri);
+    case Fp8Family::TILED3:
+      what = "fp8_gemm_tiled3 launch";
+      if (pl.wm == 2) return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 2, 4, 4>, tiled3_lds(2, 4, 1)>(what, pl, s, p3);
+      if (pl.cb == 3) return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 3>, tiled3_lds(1, 3, 1)>(what, pl, s, p3);
+      return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 4>, tiled3_lds(1, 4, 1)>(what, pl, s, p3);
+    case Fp8Family::TILED3_KS2:
+      what = "fp8_gemm_tiled3 (two k groups) launch";
+      if (pl.cb == 3) return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 3, false, 2>, tiled3_lds(1, 3, 2)>(what, pl, s, p3);
+      return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 4, false, 2>, tiled3_lds(1, 4, 2)>(what, pl, s, p3);
+    case Fp8Family::TILED3_SILU:
+      what = "fp8_gemm_tiled3 (silu * mul) launch";
+      return launch_kernel<fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 4, true>, tiled3_lds(1, 4, 1)>(what, pl, s, p3);
+    case Fp8Family::TILED3_RAWK:  // raw fp32 sums: no output type, one instantiation
+      p3.slabs = workspace;
+      p3.k_steps_per_slice = pl.k_steps_per_slice;
+      what = "fp8_gemm_tiled3 (raw split-K) launch";
+      return launch_kernel<fp8_gemm_tiled3_kernel<SGL_MI355_BF16, 3, 8, 1, 4, 4, false, 1, true>, tiled3_lds(1, 4, 1)>(what, pl, s, p3);
+    case Fp8Family::NONE: break;
+  }
+  return not_built((int)pl.fam);
+}
+
+// What every GEMM entry point does once its arguments are checked: plan, launch, report the slice count of a partials form.
+int plan_and_launch(const Fp8Shape& shape, int out_dtype, const GemmArgs& p, float* workspace, hipStream_t s, int32_t* num_slices = nullptr) {
+  const Fp8Plan pl = fp8_plan(shape, fp8_knobs());
+  const int rc = out_dtype == SGL_MI355_BF16 ? launch<SGL_MI355_BF16>(pl, p, workspace, s) : launch<SGL_MI355_FP16>(pl, p, workspace, s);
+  if (rc == 0 && num_slices != nullptr) *num_slices = pl.sk;
+  return rc;
 }
 
 }  // namespace
@@ -2470,9 +2127,8 @@ static int fp8_scaled_mm_impl(
   static const bool abl_shuf = getenv("SGL_MI355_ABL_SHUF") != nullptr;
   if (abl_shuf && shuffle_shape_ok(N, K)) p.b_shuf = 1;
 #endif
-  hipStream_t s = as_stream(stream);
-  return out_dtype == SGL_MI355_BF16 ? run_gemm<SGL_MI355_BF16>(p, workspace, workspace_floats, s)
-                                     : run_gemm<SGL_MI355_FP16>(p, workspace, workspace_floats, s);
+  return plan_and_launch(fp8_shape(Fp8Kind::MM, M, N, K, a_stride_m, b_stride_n, p.b_shuf, workspace != nullptr, workspace_floats),
+                         out_dtype, p, workspace, as_stream(stream));
 }
 
 extern "C" int sgl_mi355_fp8_scaled_mm(
@@ -2497,23 +2153,6 @@ extern "C" int sgl_mi355_fp8_scaled_mm_wshuffled(
 // sgl_mi355_silu_and_mul (fp8_utils.py:696-704, activation.py:59-83), without the [M][N] round trip through HBM.  Prefill
 // sizes on a pre-shuffled weight only: at least 192 tiles of 128 rows x 128 output columns (M = 1024 x I = 14336: 896);
 // anything else returns SGL_MI355_ERR_UNSUPPORTED WITHOUT launching and the caller makes the two calls.
-template <int OUT_DTYPE>
-static int run_gemm_silu(const GemmArgs& p, hipStream_t s) {
-  GemmArgs p3 = p;
-  static const int gn_env = [] { const char* e = getenv("SGL_MI355_T3_GN"); return e ? atoi(e) : 0; }();  // tuning aid
-  p3.raster_gn = gn_env > 0 ? gn_env : 4;
-  auto k3 = fp8_gemm_tiled3_kernel<OUT_DTYPE, 3, 8, 1, 4, 4, true>;
-  constexpr int lds_st = 3 * 128 * 128, lds_ep = 4 * 64 * 72 * 2;
-  constexpr int lds3 = lds_st > lds_ep ? lds_st : lds_ep;
-  static int a3 = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, lds3),
-                            "hipFuncSetAttribute");
-  if (a3) return a3;
-  const unsigned g3 = (unsigned)(((p.M + 127) / 128) * (((p.N >> 1) + 127) / 128));
-  g_last_kernel = "tiled3_silu";
-  hipLaunchKernelGGL(k3, dim3(g3), dim3(256), lds3, s, p3);
-  return check_hip(hipGetLastError(), "fp8_gemm_tiled3 (silu * mul) launch");
-}
-
 extern "C" int sgl_mi355_fp8_scaled_mm_silu_mul_wshuffled(
     const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b, const void* bias, void* out, int64_t M,
     int64_t N, int64_t K, int64_t a_stride_m, int out_dtype, void* stream) {
@@ -2528,16 +2167,9 @@ extern "C" int sgl_mi355_fp8_scaled_mm_silu_mul_wshuffled(
   SGLM_CHECK_ARG(reinterpret_cast<uintptr_t>(mat_a) % 16 == 0 && reinterpret_cast<uintptr_t>(mat_b) % 16 == 0 &&
                      reinterpret_cast<uintptr_t>(out) % 16 == 0,
                  "fp8_scaled_mm_silu_mul: operands must be 16-byte aligned");
-  const int64_t tiles = ((M + 127) / 128) * ((N / 2 + 127) / 128);
-  static const int min_tiles = [] { const char* e = getenv("SGL_MI355_SILU_GEMM_MIN_TILES"); return e ? atoi(e) : 192; }();  // tuning aid
-  if (M <= 64 || tiles < min_tiles) {
-    set_error("fp8_scaled_mm_silu_mul: only prefill sizes (M > 64, at least %d tiles of 128 x 128 outputs) have the fused form", min_tiles);
-    return SGL_MI355_ERR_UNSUPPORTED;
-  }
   GemmArgs p{(const uint8_t*)mat_a, a_stride_m, (const uint8_t*)mat_b, K, scales_a, scales_b, bias, out, (int)M, (int)N, (int)K};
   p.b_shuf = 1;
-  hipStream_t s = as_stream(stream);
-  return out_dtype == SGL_MI355_BF16 ? run_gemm_silu<SGL_MI355_BF16>(p, s) : run_gemm_silu<SGL_MI355_FP16>(p, s);
+  return plan_and_launch(fp8_shape(Fp8Kind::SILU_MUL, M, N, K, a_stride_m, K, 1, false, 0), out_dtype, p, nullptr, as_stream(stream));
 }
 
 // Split-K partial sums only: workspace[slice][m][n] = sum over the slice's k of a[m][k] * b[n][k] (raw fp32, no
@@ -2555,62 +2187,18 @@ static int fp8_scaled_mm_partials_impl(int b_shuf, const void* mat_a, const void
   SGLM_CHECK_ARG(mat_a && mat_b && reinterpret_cast<uintptr_t>(mat_a) % 16 == 0 && reinterpret_cast<uintptr_t>(mat_b) % 16 == 0,
                  "fp8_scaled_mm_partials: operands must be 16-byte aligned");
   *num_slices = 0;
-  if (M > 128) {
-    // prefill sizes (round 5): the tiled kernel's raw split-K form where 128 x 256 tiles alone would leave the chip half empty
-    // and K is long enough to cut -- down_proj 14336 -> 4096 at 512 / 1024 rows (tools/exp/splitk_prefill_probe.py: the GEMM body
-    // 85 -> 57 us at 1024 rows).  Everything else has no such form: the caller runs the GEMM that finishes itself.
-    const int64_t tiles = ((M + 127) / 128) * ((N + 255) / 256);
-    const int64_t steps = K >> 7;
-    int S = tiles > 0 ? (int)(256 / tiles) : 0;
-    if (S > 4) S = 4;
-    while (S >= 2 && (steps % S != 0 || (steps / S) % 4 != 0 || steps / S < 16)) --S;
-    static const bool off = getenv("SGL_MI355_NO_PREFILL_SPLITK") != nullptr;  // A/B aid
-    if (off || !b_shuf || !shuffle_shape_ok(N, K) || K < 8192 || S < 2 || (N & 7) != 0 ||
-        workspace_floats < (int64_t)S * M * N) {
-      set_error("fp8_scaled_mm_partials: no split-K form for M=%ld N=%ld K=%ld (prefill sizes: pre-shuffled weight, K >= 8192, "
-                "at most 128 tiles of 128 x 256)", (long)M, (long)N, (long)K);
-      return SGL_MI355_ERR_UNSUPPORTED;
-    }
-    GemmArgs p3{(const uint8_t*)mat_a, a_stride_m, (const uint8_t*)mat_b, K, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K};
-    p3.b_shuf = 1;
-    p3.raster_gn = 4;
-    p3.slabs = workspace;
-    p3.k_steps_per_slice = (int)(steps / S);
-    auto k3 = fp8_gemm_tiled3_kernel<SGL_MI355_BF16, 3, 8, 1, 4, 4, false, 1, true>;
-    constexpr int lds3 = 3 * 128 * 128;
-    static int a3 = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, lds3),
-                              "hipFuncSetAttribute");
-    if (a3) return a3;
-    g_last_kernel = "tiled3_rawk";
-    hipLaunchKernelGGL(k3, dim3((unsigned)tiles, (unsigned)S), dim3(256), lds3, as_stream(stream), p3);
-    int rc3 = check_hip(hipGetLastError(), "fp8_gemm_tiled3 (raw split-K) launch");
-    if (rc3) return rc3;
-    *num_slices = S;
-    return 0;
-  }
-  SGLM_CHECK_ARG(!b_shuf || shuffle_shape_ok(N, K), "fp8_scaled_mm_partials_wshuffled: N %% 16 == 0 and K %% 512 == 0 required");
+  // (above 128 rows a pre-shuffled weight of another granularity is "no split-K form", not a bad argument)
+  SGLM_CHECK_ARG(M > 128 || !b_shuf || shuffle_shape_ok(N, K), "fp8_scaled_mm_partials_wshuffled: N %% 16 == 0 and K %% 512 == 0 required");
   GemmArgs p{(const uint8_t*)mat_a, a_stride_m, (const uint8_t*)mat_b, b_stride_n, nullptr, nullptr, nullptr, nullptr,
              (int)M, (int)N, (int)K};
   p.b_shuf = b_shuf;
 #if SGLM_ABL_SHUF  // timing ablation, see fp8_scaled_mm_impl
   static const bool abl_shuf = getenv("SGL_MI355_ABL_SHUF") != nullptr;
-  if (abl_shuf && shuffle_shape_ok(N, K)) p.b_shuf = 1;
+  if (M <= 128 && abl_shuf && shuffle_shape_ok(N, K)) p.b_shuf = 1;
 #endif
-  hipStream_t s = as_stream(stream);
-  bool used = false;
-  int sk = 0;
-  int rc = M <= 16   ? launch_wstream<SGL_MI355_BF16, 1>(p, workspace, workspace_floats, s, used, &sk)
-           : M <= 32 ? launch_wstream<SGL_MI355_BF16, 2>(p, workspace, workspace_floats, s, used, &sk)
-           : M <= 64 ? launch_wstream<SGL_MI355_BF16, 4>(p, workspace, workspace_floats, s, used, &sk)
-                     : launch_wstream<SGL_MI355_BF16, 8>(p, workspace, workspace_floats, s, used, &sk);  // 128-row phases
-  if (rc) return rc;
-  if (!used) {
-    set_error("fp8_scaled_mm_partials: shape (M=%ld N=%ld K=%ld) is not on the split-K weight-streaming path", (long)M,
-              (long)N, (long)K);
-    return SGL_MI355_ERR_UNSUPPORTED;
-  }
-  *num_slices = sk;
-  return 0;
+  // raw fp32 sums have no output type: the BF16 instantiations serve
+  return plan_and_launch(fp8_shape(Fp8Kind::PARTIALS, M, N, K, a_stride_m, b_stride_n, p.b_shuf, true, workspace_floats), SGL_MI355_BF16, p,
+                         workspace, as_stream(stream), num_slices);
 }
 
 extern "C" int sgl_mi355_fp8_scaled_mm_partials(const void* mat_a, const void* mat_b, float* workspace,
@@ -2653,32 +2241,11 @@ extern "C" int sgl_mi355_fp8_scaled_mm_partials_a16(const void* mat_a16, int64_t
   SGLM_CHECK_ARG(!b_shuffled || shuffle_shape_ok(N, K), "fp8_scaled_mm_partials_a16: N %% 16 == 0 and K %% 512 == 0 required for a pre-shuffled weight");
   SGLM_CHECK_ARG(b_shuffled || (b_stride_n % 16 == 0 && b_stride_n >= K), "fp8_scaled_mm_partials_a16: bad weight row stride");
   *num_slices = 0;
-  if (M > 64) {
-    set_error("fp8_scaled_mm_partials_a16: only the decode kernels (M <= 64) have this form");
-    return SGL_MI355_ERR_UNSUPPORTED;
-  }
   GemmArgs p{nullptr, K, (const uint8_t*)mat_b, b_shuffled ? K : b_stride_n, nullptr, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K};
   p.b_shuf = b_shuffled ? 1 : 0;
   p.a16 = mat_a16; p.a16_sm = a_stride_m; p.a_absmax = row_absmax; p.a_scale_out = scales_a_out;
-  hipStream_t s = as_stream(stream);
-  bool used = false;
-  int sk = 0;
-  int rc;
-  if (a_dtype == SGL_MI355_BF16)
-    rc = M <= 16   ? launch_wstream<SGL_MI355_BF16, 1>(p, workspace, workspace_floats, s, used, &sk)
-         : M <= 32 ? launch_wstream<SGL_MI355_BF16, 2>(p, workspace, workspace_floats, s, used, &sk)
-                   : launch_wstream<SGL_MI355_BF16, 4>(p, workspace, workspace_floats, s, used, &sk);
-  else
-    rc = M <= 16   ? launch_wstream<SGL_MI355_FP16, 1>(p, workspace, workspace_floats, s, used, &sk)
-         : M <= 32 ? launch_wstream<SGL_MI355_FP16, 2>(p, workspace, workspace_floats, s, used, &sk)
-                   : launch_wstream<SGL_MI355_FP16, 4>(p, workspace, workspace_floats, s, used, &sk);
-  if (rc) return rc;
-  if (!used) {
-    set_error("fp8_scaled_mm_partials_a16: shape (M=%ld N=%ld K=%ld) has no single-phase split-K form", (long)M, (long)N, (long)K);
-    return SGL_MI355_ERR_UNSUPPORTED;
-  }
-  *num_slices = sk;
-  return 0;
+  return plan_and_launch(fp8_shape(Fp8Kind::PARTIALS_A16, M, N, K, a_stride_m, b_stride_n, p.b_shuf, true, workspace_floats), a_dtype, p,
+                         workspace, as_stream(stream), num_slices);
 #endif
 }
 
@@ -2717,3 +2284,16 @@ extern "C" int sgl_mi355_fp8_shuffle_weight(const void* src, void* dst, int64_t 
 }
 
 extern "C" const char* sgl_mi355_fp8_last_kernel(void) { return g_last_kernel; }
+
+// The plan the entry point of `kind` would launch for this shape (include/sgl_mi355.h): host arithmetic only.
+extern "C" int sgl_mi355_fp8_gemm_plan(int kind, int64_t M, int64_t N, int64_t K, int64_t a_stride_m, int64_t b_stride_n, int b_shuffled,
+                                       int has_workspace, int64_t workspace_floats, sgl_mi355_fp8_plan* plan) {
+  SGLM_CHECK_ARG(plan != nullptr && kind >= SGL_MI355_FP8_PLAN_MM && kind <= SGL_MI355_FP8_PLAN_SILU_MUL,
+                 "fp8_gemm_plan: null plan / unknown kind %d", kind);
+  SGLM_CHECK_ARG(M > 0 && N > 0 && K > 0 && N < (1ll << 31) && K < (1ll << 31), "fp8_gemm_plan: bad shape");
+  const Fp8Plan pl = fp8_plan(fp8_shape((Fp8Kind)kind, M, N, K, a_stride_m, b_stride_n, b_shuffled, has_workspace != 0, workspace_floats),
+                              fp8_knobs());
+  *plan = pl;
+  if (pl.rc) set_error("%s", pl.error);
+  return pl.rc;
+}

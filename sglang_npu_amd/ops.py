@@ -8,6 +8,7 @@ the host and nothing falls back to PyTorch.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import weakref
@@ -721,6 +722,35 @@ def fp8_last_kernel() -> str:
     f = _lib.lib().sgl_mi355_fp8_last_kernel
     f.restype = ctypes.c_char_p
     return f().decode()
+
+
+_FP8_PLAN_KINDS = {"mm": 0, "partials": 1, "partials_a16": 2, "silu_mul": 3}
+_FP8_PLAN_INTS = ("mb", "ph", "s", "nb", "wk", "exact", "nstage", "ri", "wm", "wn", "cb", "ks", "silu", "rawk", "scaled",
+                  "grid_x", "grid_y", "block", "lds", "sk", "per_slice", "waves", "groups", "raster_gn", "k_steps_per_slice", "finalize")
+
+
+class _Fp8PlanStruct(ctypes.Structure):  # sgl_mi355_fp8_plan (include/sgl_mi355.h)
+    _fields_ = [("family", ctypes.c_char * 16)] + [(n, ctypes.c_int32) for n in _FP8_PLAN_INTS]
+
+
+Fp8GemmPlan = collections.namedtuple("Fp8GemmPlan", ("rc", "error", "family") + _FP8_PLAN_INTS)
+
+
+def fp8_gemm_plan(M: int, N: int, K: int, shuffled: bool, workspace_floats: Optional[int] = None, kind: str = "mm",
+                  a_stride: Optional[int] = None, b_stride: Optional[int] = None) -> Fp8GemmPlan:
+    """The kernel an FP8 GEMM call of this shape launches and how (csrc/gemm_fp8_plan.h fp8_plan; fields: sgl_mi355_fp8_plan).
+    Host arithmetic only: no GPU needed.  rc 2 and `error`: the call would be refused as unsupported.
+    workspace_floats: None = what fp8_scaled_mm itself passes; 0 = no workspace."""
+    if workspace_floats is None:
+        workspace_floats = max(_fp8_workspace.floor, _fp8_slab_floats(M, N, K)) if 0 < M <= 256 else 0
+    plan = _Fp8PlanStruct()
+    rc = _lib.lib().sgl_mi355_fp8_gemm_plan(
+        _I(_FP8_PLAN_KINDS[kind]), _I64(M), _I64(N), _I64(K), _I64(K if a_stride is None else a_stride),
+        _I64(K if b_stride is None else b_stride), _I(1 if shuffled else 0), _I(1 if workspace_floats > 0 else 0),
+        _I64(workspace_floats), ctypes.byref(plan))
+    if rc not in (0, 2):
+        _lib.check(rc)
+    return Fp8GemmPlan(rc, _lib.last_error() if rc else "", plan.family.decode(), *(getattr(plan, n) for n in _FP8_PLAN_INTS))
 
 
 def fp8_shuffle_weight(weight: torch.Tensor, inverse: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -41,12 +41,15 @@ def _fp8_check(M, N, K, shuffled, dt, bias, seed, family=None, partials=False, s
             part = ops.fp8_scaled_mm_partials(a, wt, c.sa, c.sb, dt, c.bias)
             assert part is not None, f"{what}: no partials form"
             names.append(ops.fp8_last_kernel())
+            plan = ops.fp8_gemm_plan(M, N, K, shuffled, part.ws.numel(), "partials", a.stride(0) if M > 1 else K)
             if slices is not None:
                 assert slices[0] <= part.num_slices <= slices[1], (what, part.num_slices)
             out = part.finalize()
         else:
             out = ops.fp8_scaled_mm(a, wt, c.sa, c.sb, dt, c.bias)
             names.append(ops.fp8_last_kernel())
+            plan = ops.fp8_gemm_plan(M, N, K, shuffled, a_stride=a.stride(0) if M > 1 else K)
+        assert plan.family == names[-1], f"{what}: the plan says '{plan.family}', '{names[-1]}' ran"
         if family is not None:
             assert names[-1] == family, f"{what}: ran '{names[-1]}', the case is meant for '{family}'"
         eg.assert_bits_equal(out, c.ref, f"{what} [{names[-1]}]", c.step)
@@ -182,6 +185,7 @@ def test_fp8_70b_rank_shapes_are_exact_on_both_layouts(M, N, K):
         what = f"70B rank shape M={M} N={N} K={K} {'shuffled' if shuffled else 'row-major'} {dt} bias={bias}"
         out = ops.fp8_scaled_mm(c.a, wt, c.sa, c.sb, dt, c.bias)
         eg.assert_bits_equal(out, c.ref, f"{what} [{ops.fp8_last_kernel()}]", c.step)
+        assert ops.fp8_gemm_plan(M, N, K, shuffled).family == ops.fp8_last_kernel(), what
         part = ops.fp8_scaled_mm_partials(c.a, wt, c.sa, c.sb, dt, c.bias)
         if part is not None:  # the split-K half, wherever it is offered
             name = ops.fp8_last_kernel()
