@@ -34,7 +34,7 @@ extern "C" {
 #define SGL_MI355_ERR_RUNTIME 3          /* a HIP runtime call failed                */
 
 /* ABI version of this header; bumped on any signature change. */
-#define SGL_MI355_ABI_VERSION 16
+#define SGL_MI355_ABI_VERSION 17
 int sgl_mi355_abi_version(void);
 
 /* Copies the calling thread's last error message (NUL-terminated) into buf. Returns its length. */
@@ -418,6 +418,36 @@ int sgl_mi355_fp8_scaled_mm(
     const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b, const void* bias, void* out,
     float* workspace, int64_t workspace_floats,
     int64_t M, int64_t N, int64_t K, int64_t a_stride_m, int64_t b_stride_n, int out_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * W8A8 INT8 linear: dynamic per-token activation quant + INT8 x INT8 GEMM with per-row / per-column scales (ABI 17).
+ * Replaces: per_token_quant_int8(x) -> (x_q, scale), as called by W8A8Int8LinearMethod.apply
+ *           python/sglang/srt/layers/quantization/w8a8_int8.py:390 (definition: test/srt/cpu/utils.py:23-31)
+ *   absmax = max(max_k |x|, 1e-10); output_s[t] = absmax / 127; output_q = (int8) rint(x * (127 / absmax)), fp32, ties to
+ *   even.  input [T, K] bf16 / fp16 contiguous, K % 16 == 0; output_q int8 [T, K]; output_s fp32 [T].  Bit-exact. */
+int sgl_mi355_per_token_quant_int8(const void* input, void* output_q, float* output_s, int64_t num_tokens,
+                                   int64_t hidden_dim, int dtype, void* stream);
+/* Replaces: int8_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype,
+ *                          Tensor? bias) -> Tensor
+ *           schema sgl-kernel/csrc/common_extension.cc:102-104, impl sgl-kernel/csrc/gemm/int8_gemm_kernel.cu:663-745
+ *           (epilogue cutlass_extensions/epilogue/epilogue_per_row_per_col_scale.h:278,301)
+ *   out[m,n] = cast(f32(sum_k a[m,k] b[k,n])_i32 * (scales_b[n] * scales_a[m]) (+ bias[n])), every fp32 step rounded on its
+ *   own (no fma): bit-exact for any K slicing.  mat_a [M,K] int8 row-major (a_stride_m bytes between rows); mat_b [K,N]
+ *   int8 with stride(0) == 1, i.e. its K-major storage W[N][K] (b_stride_n bytes between columns); scales fp32 contiguous
+ *   [M] / [N]; bias [N] in out dtype or NULL; out [M,N] contiguous bf16/fp16.  K % 16 == 0 and N % 8 == 0 as in the
+ *   reference (int8_gemm_kernel.cu:677-679).  `workspace` (int32, caller-owned, may be NULL when M > 64 or K <= 2048)
+ *   holds the split-K partial sums of the M <= 64 weight streamer: ceil(K / 2048) * M * N int32.
+ * _wshuffled: mat_b in the fragment-major byte layout of sgl_mi355_fp8_shuffle_weight (N % 16 == 0, K % 512 == 0; no
+ *   b_stride_n); results bit-identical to the row-major call. */
+int sgl_mi355_int8_scaled_mm(const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b,
+                             const void* bias, void* out, int32_t* workspace, int64_t workspace_ints, int64_t M, int64_t N,
+                             int64_t K, int64_t a_stride_m, int64_t b_stride_n, int out_dtype, void* stream);
+int sgl_mi355_int8_scaled_mm_wshuffled(const void* mat_a, const void* mat_b, const float* scales_a, const float* scales_b,
+                                       const void* bias, void* out, int32_t* workspace, int64_t workspace_ints, int64_t M,
+                                       int64_t N, int64_t K, int64_t a_stride_m, int out_dtype, void* stream);
+/* Test aid: the kernel family the last sgl_mi355_int8_scaled_mm* call of the calling thread launched ("int8_stream",
+ * "int8_stream_rowmajor", "int8_tiled"; "" before the first call).  Replaces: nothing (like sgl_mi355_fp8_last_kernel). */
+const char* sgl_mi355_int8_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------
  * AWQ INT4 (group-wise zero-point) weight-only path.

@@ -918,6 +918,132 @@ def fp8_blockwise_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=No
     return out
 
 
+# --------------------------------------------------------------------------- INT8 w8a8
+def per_token_quant_int8(x: torch.Tensor):
+    """per_token_quant_int8(x) -> (x_q int8, scale fp32 [..., 1]) -- as W8A8Int8LinearMethod.apply calls it (w8a8_int8.py:390;
+    definition test/srt/cpu/utils.py:23-31): scale = max(absmax, 1e-10) / 127, x_q = rint(x * (127 / absmax)), bit-exact."""
+    _need_gpu(x)
+    K = x.shape[-1]
+    if K % 16 != 0:
+        raise RuntimeError(f"per_token_quant_int8: the hidden dimension must be a multiple of 16, got {K}")
+    x2 = x.reshape(-1, K)
+    x2 = x2 if x2.is_contiguous() else x2.contiguous()
+    q = torch.empty(x2.shape, dtype=torch.int8, device=x.device)
+    s = torch.empty((x2.shape[0], 1), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().sgl_mi355_per_token_quant_int8(_ptr(x2), _ptr(q), _ptr(s), _I64(x2.shape[0]), _I64(K),
+                                                         _I(_dtype_code(x2)), _stream(x2)))
+    return q.view(x.shape), s.view(x.shape[:-1] + (1,))
+
+
+def int8_shuffle_supported(N: int, K: int) -> bool:
+    return fp8_shuffle_supported(N, K)
+
+
+def _is_int8_wshuffled(w: torch.Tensor) -> bool:
+    """The fragment-major form of an INT8 weight: contiguous int8 [N / 16, 16 K] (K % 512 == 0)."""
+    return (w.dtype == torch.int8 and w.dim() == 2 and w.shape[0] > 0 and w.shape[1] > 0 and w.shape[1] % _WSHUF_ROW == 0
+            and w.is_contiguous())
+
+
+def int8_shuffle_weight(weight: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """Row-major int8 weight [N, K] -> contiguous int8 [N / 16, 16 K] in the fragment-major byte layout of fp8_shuffle_weight
+    (the same kernel: the layout is a byte layout); inverse=True: back to row-major [N, K]."""
+    _need_gpu(weight)
+    if weight.dtype != torch.int8 or weight.dim() != 2:
+        raise RuntimeError("int8_shuffle_weight: a 2-D int8 weight is required")
+    if inverse:
+        if not _is_int8_wshuffled(weight):
+            raise RuntimeError("int8_shuffle_weight(inverse): the contiguous fragment-major int8 tensor [N / 16, 16 K] is required")
+        N, K = weight.shape[0] * 16, weight.shape[1] // 16
+        res = torch.empty((N, K), dtype=torch.int8, device=weight.device)
+        _lib.check(_lib.lib().sgl_mi355_fp8_shuffle_weight(_ptr(weight), _ptr(res), _I64(N), _I64(K), _I64(K), _I(1),
+                                                           _stream(weight)))
+        return res
+    if weight.stride(1) != 1:
+        raise RuntimeError("int8_shuffle_weight: a weight [N, K] with contiguous rows is required")
+    N, K = weight.shape
+    if not int8_shuffle_supported(N, K):
+        raise RuntimeError(f"int8_shuffle_weight: N % 16 == 0 and K % 512 == 0 required, got N={N} K={K}")
+    res = torch.empty((N // 16, 16 * K), dtype=torch.int8, device=weight.device)
+    _lib.check(_lib.lib().sgl_mi355_fp8_shuffle_weight(_ptr(weight), _ptr(res), _I64(N), _I64(K), _I64(weight.stride(0)),
+                                                       _I(0), _stream(weight)))
+    return res
+
+
+def int8_last_kernel() -> str:
+    """Kernel family launched by this thread's last int8_scaled_mm call (test aid)."""
+    f = _lib.lib().sgl_mi355_int8_last_kernel
+    f.restype = ctypes.c_char_p
+    return f().decode()
+
+
+def int8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> torch.Tensor:
+    """sgl_kernel.int8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None)
+    -- sgl-kernel/python/sgl_kernel/gemm.py, int8_gemm_kernel.cu:663-745 (same checks, same messages).
+    mat_b is told apart by structure, as for FP8: an int8 tensor with stride(0) == 1 is the reference's column-major [K, N];
+    a contiguous int8 [N / 16, 16 K] with K == mat_a.shape[1] is the fragment-major tensor of int8_shuffle_weight (it can
+    never have stride(0) == 1); anything else is an error."""
+    _need_gpu(mat_a, mat_b, scales_a, scales_b, bias)
+    if mat_a.dim() != 2:
+        raise RuntimeError("mat_a must be a 2D tensor")
+    if mat_b.dim() != 2:
+        raise RuntimeError("mat_b must be a 2D tensor")
+    if mat_a.stride(1) != 1:
+        raise RuntimeError("mat_a must be a row major tensor")
+    if mat_a.dtype != torch.int8:
+        raise RuntimeError("mat_a must be Int8")
+    if mat_b.dtype != torch.int8:
+        raise RuntimeError("mat_b must be Int8")
+    M, K = mat_a.shape
+    if mat_b.stride(0) == 1:
+        shuf = False
+        if K != mat_b.size(0):
+            raise RuntimeError("mat_a and mat_b shapes cannot be multiplied")
+        N = mat_b.size(1)
+        b_stride_n = mat_b.stride(1) if N > 1 else K
+    elif _is_int8_wshuffled(mat_b) and mat_b.shape[1] == 16 * K:
+        shuf, N, b_stride_n = True, mat_b.shape[0] * 16, K
+    else:
+        raise RuntimeError("mat_a must be a column major tensor")  # (sic: int8_gemm_kernel.cu:675)
+    if K % 16 != 0:
+        raise RuntimeError("mat_a.size(1) must be multiple of 16 for memory alignment")
+    if N % 8 != 0:
+        raise RuntimeError("mat_b.size(1) must be multiple of 8 for memory alignment")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("out_dtype must be Half or BFloat16")
+    if scales_a.numel() != M:
+        raise RuntimeError("size of scales_a is not matched")
+    if scales_b.numel() != N:
+        raise RuntimeError("size of scales_b is not matched")
+    if not scales_a.is_contiguous():
+        raise RuntimeError("scales_a must be contiguous")
+    if not scales_b.is_contiguous():
+        raise RuntimeError("scales_b msut be contiguous")  # (sic: int8_gemm_kernel.cu:687)
+    if scales_a.dtype != torch.float32:
+        raise RuntimeError("scales_a must be Float32")
+    if scales_b.dtype != torch.float32:
+        raise RuntimeError("scales_b must be Float32")
+    if bias is not None:
+        if bias.numel() != N:
+            raise RuntimeError("size of bias is not matched")
+        if not bias.is_contiguous():
+            raise RuntimeError("bias must be contiguous")
+        if bias.dtype != out_dtype:
+            raise RuntimeError("bias dtype must match output dtype")
+    out = torch.empty((M, N), dtype=out_dtype, device=mat_a.device)
+    # the M <= 64 weight streamer cuts K into slices of 2048 (gemm_int8.hip: its LDS capacity) and keeps int32 partial sums
+    slices = -(-K // 2048) if 0 < M <= 64 else 1
+    ws = _fp8_workspace.get(mat_a.device, slices * M * N).view(torch.int32) if slices > 1 else None
+    common = (_ptr(mat_a), _ptr(mat_b), _ptr(scales_a), _ptr(scales_b), _ptr(bias), _ptr(out), _ptr(ws),
+              _I64(ws.numel() if ws is not None else 0), _I64(M), _I64(N), _I64(K), _I64(mat_a.stride(0) if M > 1 else K))
+    tail = (_I(0 if out_dtype == torch.bfloat16 else 1), _stream(mat_a))
+    if shuf:
+        _lib.check(_lib.lib().sgl_mi355_int8_scaled_mm_wshuffled(*common, *tail))
+    else:
+        _lib.check(_lib.lib().sgl_mi355_int8_scaled_mm(*common, _I64(b_stride_n), *tail))
+    return out
+
+
 def fp8_scaled_mm_silu_mul(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> Optional[torch.Tensor]:
     """silu_and_mul(fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias)) in ONE launch -- the gate_up GEMM of a
     gated MLP (mat_b = [gate | up] columns) with the activation in its epilogue: [M, N/2], bit-identical to the two calls.

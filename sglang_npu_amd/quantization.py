@@ -3,6 +3,7 @@
 Interface mirrored (same method names / argument meaning):
   QuantizationConfig / LinearMethodBase   python/sglang/srt/layers/quantization/base_config.py:15-80,113-203
   W8A8Fp8Config / W8A8Fp8LinearMethod      python/sglang/srt/layers/quantization/w8a8_fp8.py:34-189
+  W8A8Int8Config / W8A8Int8LinearMethod    python/sglang/srt/layers/quantization/w8a8_int8.py:184-394
   Fp8Config / Fp8LinearMethod (block FP8)   python/sglang/srt/layers/quantization/fp8.py:110-190, 221-361, 462-480
   apply_fp8_linear                          python/sglang/srt/layers/quantization/fp8_utils.py:510-533,653-704
   AWQConfig / AWQLinearMethod               python/sglang/srt/layers/quantization/awq.py:75-150,319-418
@@ -25,6 +26,7 @@ from __future__ import annotations
 from typing import Any, Dict, List, Optional
 
 import os
+import re
 
 import torch
 
@@ -512,6 +514,99 @@ class Fp8LinearMethod(LinearMethodBase):
         return out.view(*x.shape[:-1], out.shape[-1])
 
 
+# ----------------------------------------------------------------------------- INT8 w8a8
+def _ignored(prefix: str, ignore: List[str], fused_mapping: Dict[str, List[str]]) -> bool:
+    """compressed_tensors/utils.py:21-73 (should_ignore_layer): a name is ignored when it equals an entry of `ignore` or matches
+    one written as ``re:<pattern>``; a fused layer (qkv_proj, gate_up_proj) that is not listed itself is asked shard by shard
+    under the checkpoint's names, and its shards must agree."""
+    def hit(name):
+        return any(re.match(t[3:], name) is not None if t.startswith("re:") else t == name for t in ignore)
+    proj = prefix.split(".")[-1]
+    if proj in fused_mapping and prefix not in ignore:
+        hits = {hit(prefix.replace(proj, shard)) for shard in fused_mapping[proj]}
+        if len(hits) > 1:
+            raise ValueError(f"Found different quantization schemes for {fused_mapping[proj]} in {prefix}: the shards of a "
+                             "fused layer must all be quantised or all be ignored.")
+        return hits.pop()
+    return hit(prefix)
+
+
+class W8A8Int8Config(QuantizationConfig):
+    """w8a8_int8.py:184-290 without its NPU branches: static per-channel symmetric INT8 weights, dynamic per-token symmetric
+    INT8 activations."""
+
+    def __init__(self, quant_config: Optional[Dict[str, Any]] = None):
+        quant_config = quant_config or {}
+        self.quant_description = quant_config
+        self.is_dynamic = quant_config.get("is_dynamic", False)
+        self.ignore = quant_config.get("ignore") or []
+        self.packed_modules_mapping = quant_config.get("packed_modules_mapping") or {}
+
+    def get_name(self) -> str:
+        return "w8a8_int8"
+
+    def get_supported_act_dtypes(self):
+        return [torch.float16, torch.bfloat16]
+
+    @classmethod
+    def get_min_capability(cls) -> int:
+        return 75
+
+    @staticmethod
+    def get_config_filenames():
+        return []
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(config)
+
+    def get_quant_method(self, layer, prefix: str):
+        if _ignored(prefix, self.ignore, self.packed_modules_mapping):
+            return UnquantizedLinearMethod()
+        if is_linear_layer(layer):
+            return W8A8Int8LinearMethod(self)
+        return None
+
+
+class W8A8Int8LinearMethod(LinearMethodBase):
+    """w8a8_int8.py:327-394: ``weight`` int8 [N, K], ``weight_scale`` fp32 [N, 1]; apply = ops.per_token_quant_int8 then
+    ops.int8_scaled_mm (csrc/quant_int8.hip, csrc/gemm_int8.hip), two launches."""
+
+    def __init__(self, quantization_config: W8A8Int8Config):
+        self.quantization_config = quantization_config
+
+    def create_weights(self, layer, input_size_per_partition, output_partition_sizes, input_size, output_size,
+                       params_dtype, **extra_weight_attrs):
+        P = _param_classes()
+        weight_loader = extra_weight_attrs.get("weight_loader")
+        n = sum(output_partition_sizes)
+        self.logical_widths = output_partition_sizes
+        layer.register_parameter("weight", P.ModelWeightParameter(
+            data=torch.empty(n, input_size_per_partition, dtype=torch.int8), input_dim=1, output_dim=0,
+            weight_loader=weight_loader))
+        layer.register_parameter("weight_scale", P.ChannelQuantScaleParameter(
+            data=torch.empty((n, 1), dtype=torch.float32), output_dim=0, weight_loader=weight_loader))
+
+    def process_weights_after_loading(self, layer) -> None:
+        weight = layer.weight
+        if getattr(layer, "_sgl_mi355_int8_done", False):
+            return  # re-entered (W8A8Fp8LinearMethod: the bytes are already laid out and the storage must not change)
+        n, k = weight.shape
+        if PRESHUFFLE_FP8_WEIGHTS and weight.is_cuda and ops.int8_shuffle_supported(n, k):
+            # fragment-major bytes, as for FP8: a contiguous int8 [N / 16, 16 K] tensor, told apart from [K, N] by structure
+            layer.weight = torch.nn.Parameter(ops.int8_shuffle_weight(weight.data.contiguous()), requires_grad=False)
+        else:
+            layer.weight = torch.nn.Parameter(weight.data.t(), requires_grad=False)  # w8a8_int8.py:340: K-major [K, N] view
+        layer.weight_scale = torch.nn.Parameter(layer.weight_scale.data, requires_grad=False)
+        layer._sgl_mi355_int8_done = True
+
+    def apply(self, layer, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        x_q, x_scale = ops.per_token_quant_int8(x)
+        out = ops.int8_scaled_mm(x_q.view(-1, x_q.shape[-1]), layer.weight, x_scale.view(-1, 1), layer.weight_scale,
+                                 out_dtype=x.dtype, bias=bias)
+        return out.view(*x.shape[:-1], out.shape[-1])
+
+
 # ----------------------------------------------------------------------------- AWQ INT4
 class AWQConfig(QuantizationConfig):
     """awq.py:75-150."""
@@ -657,6 +752,7 @@ class AWQLinearMethod(LinearMethodBase):
 QUANTIZATION_METHODS = {
     "w8a8_fp8": W8A8Fp8Config,
     "fp8": Fp8Config,
+    "w8a8_int8": W8A8Int8Config,
     "awq": AWQConfig,
 }
 

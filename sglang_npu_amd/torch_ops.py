@@ -28,6 +28,7 @@ from . import ops
 _SCHEMAS = {
     # sgl-kernel/csrc/common_extension.cc:98-130
     "awq_dequantize": "(Tensor qweight, Tensor scales, Tensor qzeros) -> Tensor",
+    "int8_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype, Tensor? bias) -> Tensor",
     "fp8_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype, Tensor? bias) -> Tensor",
     "fp8_blockwise_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype) -> Tensor",
     "sgl_per_token_group_quant_fp8": "(Tensor input, Tensor output_q, Tensor output_s, int group_size, float eps, "
@@ -83,6 +84,7 @@ def _apply_rope(q, k, q_rope, k_rope, cos_sin_cache, pos_ids, interleave, cuda_s
 
 _IMPLS = {
     "awq_dequantize": ops.awq_dequantize,
+    "int8_scaled_mm": ops.int8_scaled_mm,
     "fp8_scaled_mm": ops.fp8_scaled_mm,
     "fp8_blockwise_scaled_mm": ops.fp8_blockwise_scaled_mm,
     "sgl_per_token_group_quant_fp8": ops.sgl_per_token_group_quant_fp8,
