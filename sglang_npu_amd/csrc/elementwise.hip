@@ -65,7 +65,8 @@ __device__ __forceinline__ uint2 pack8_fp8(const float* f) {
 #define SGLM_ABL_ROWSPLIT 0  // timing ablation (WRONG RESULTS): the from-partials row owners of decode batches as FOUR workgroups per row, each
                              // a quarter of the columns, no exchange of the row statistics (what would a row split buy at best?)
 #endif
-template <int DTYPE, int VPT, bool FROM_PARTIALS = false, int NT = 256, int RS = 1>
+// SU (FROM_PARTIALS): slices fetched at a time, 4 or 8 -- the launcher takes 4 when there are at most four (gemm_row8, partials.h)
+template <int DTYPE, int VPT, bool FROM_PARTIALS = false, int NT = 256, int RS = 1, int SU = 8>
 __global__ __launch_bounds__(NT) void rmsnorm_kernel(
     const typename Half16<DTYPE>::T* x /* may alias out */, typename Half16<DTYPE>::T* residual,
     const typename Half16<DTYPE>::T* __restrict__ weight, typename Half16<DTYPE>::T* out,
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(
       x8 rv;
       if (residual) rv = reinterpret_cast<const x8*>(residual + row * H)[vi];
       x8 xv;
-      if constexpr (FROM_PARTIALS) xv = gemm_row8<DTYPE>(ps, row, 8 * vi);
+      if constexpr (FROM_PARTIALS) xv = gemm_row8<DTYPE, SU>(ps, row, 8 * vi);
       else xv = reinterpret_cast<const x8*>(x + row * H)[vi];
       if (residual) {
         x8 nr;
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(
 // the row is latency- and ALU-bound (an exp and a divide per element), not bandwidth-bound.
 // FROM_PARTIALS: x is not materialised -- gate and up columns come from the split-K partials of the gate_up GEMM
 // (gemm_row8: slice sums + the reference epilogue, rounded to the 16-bit dtype first, so bit-identical to the unfused path).
-template <int DTYPE, int VPT, int NT, bool FROM_PARTIALS = false, int RS = 1>
+template <int DTYPE, int VPT, int NT, bool FROM_PARTIALS = false, int RS = 1, int SU = 8>
 __global__ __launch_bounds__(NT) void silu_mul_kernel(
     const typename Half16<DTYPE>::T* __restrict__ x, typename Half16<DTYPE>::T* __restrict__ out,
     uint8_t* __restrict__ out_q, float* __restrict__ out_s, int d, PartialSrc ps = PartialSrc{}) {
@@ -165,8 +166,8 @@ __global__ __launch_bounds__(NT) void silu_mul_kernel(
     if (vi - vbase < nv) {
       x8 a, b;
       if constexpr (FROM_PARTIALS) {
-        a = gemm_row8<DTYPE>(ps, row, vi * 8);
-        b = gemm_row8<DTYPE>(ps, row, d + vi * 8);
+        a = gemm_row8<DTYPE, SU>(ps, row, vi * 8);
+        b = gemm_row8<DTYPE, SU>(ps, row, d + vi * 8);
       } else {
         a = reinterpret_cast<const x8*>(x + row * 2 * d)[vi];
         b = reinterpret_cast<const x8*>(x + row * 2 * d + d)[vi];
@@ -245,50 +246,90 @@ __device__ __forceinline__ void pool_store(char* row, int i, typename Half16<DTY
 // pool rows loc[t] in the same pass -- one launch instead of rope + set_kv_buffer, and k/v are not re-read.
 // One 64-thread wave per (token, head) over q heads, then k heads (which also carry v).
 // RoPE + KV write straight from the split-K partials of the qkv GEMM: column c of the [T, (Hq + 2 Hk) D] qkv row is
-// produced on the fly (gemm_elem), q goes (rotated) to q_out [T, Hq D], k (rotated) and v to the pool.
-template <int DTYPE, typename LocT, int KV8>
+// produced on the fly (elem_issue / elem_finish, partials.h), q goes (rotated) to q_out [T, Hq D], k (rotated) and v to the pool.
+// The kernel is a chain of memory round trips, not bandwidth, so the work is cut into 64-thread waves that each make TWO trips
+// -- the per-token scalars (cos | sin sit behind positions[t], the pool row behind loc[t]), then every vector load -- and issue
+// every load before their first store (the stores go through char* the compiler cannot tell from ps.partials, so a load
+// behind one would wait for it):
+//   * a rotation wave per (token, q or k head, 64 pairs): one pair per lane;
+//   * a copy wave per (token, v head, 64 elements) -- v needs no rotation and nothing from k -- and, where rot_dim < D, per
+//     (token, q or k head, 64 pass-through elements): one element per lane.
+// D = 128, full rotation: Hq + 3 Hk waves per token.  Lanes past the end of their run fetch its last element again (no load
+// under a branch) and store nothing.  SU: slices fetched at a time (4 or 8, see partials.h).
+template <int DTYPE, typename LocT, int KV8, int SU>
 __global__ __launch_bounds__(256) void rope_kv_from_partials_kernel(
     typename Half16<DTYPE>::T* __restrict__ q_out, char* __restrict__ kb,
     char* __restrict__ vb, const int64_t* __restrict__ positions, const LocT* __restrict__ loc,
     const float* __restrict__ cache, int64_t T, int Hq, int Hk, int D, int rot_dim, int64_t q_st, int64_t kb_sn,
     int64_t kb_sh, int64_t vb_sn, int64_t vb_sh, int neox, PartialSrc ps) {
   using Hh = Half16<DTYPE>;
+  using T16 = typename Hh::T;
   const int lane = threadIdx.x & 63;
-  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t total = T * (int64_t)(Hq + Hk);
-  if (item >= total) return;
-  const int h = (int)(item % (Hq + Hk));
-  const int64_t t = item / (Hq + Hk);
-  const bool is_k = h >= Hq;
-  const int col0 = h * D;  // q heads then k heads are contiguous in the qkv row
-  const float* cs = cache + positions[t] * rot_dim;
-  const int half = rot_dim >> 1;
+  // the wave index as a scalar: token and head are wave-uniform, so positions[t], loc[t] and the row scale are scalar loads
+  const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int half = rot_dim >> 1, npass = D - rot_dim;
+  const int PC = (half + 63) >> 6, VC = (D + 63) >> 6, NC = (npass + 63) >> 6;  // waves per head: pairs, v, pass-through
+  const int n_rot = (Hq + Hk) * PC, n_v = Hk * VC;
+  const int W = n_rot + n_v + (Hq + Hk) * NC;  // waves per token (the launcher computes the same)
+  if (item >= T * (int64_t)W) return;
+  const int64_t t = item / W;
+  int w = (int)(item % W);
   constexpr int ES = KV8 ? 1 : 2;  // bytes per pool element
-  typename Hh::T* qdst = q_out + t * q_st + (int64_t)h * D;
-  char* kdst = is_k ? kb + ((int64_t)loc[t] * kb_sn + (int64_t)(h - Hq) * kb_sh) * ES : nullptr;
-  for (int p = lane; p < half; p += 64) {
-    const int i1 = neox ? p : 2 * p, i2 = neox ? p + half : 2 * p + 1;
-    const float c = cs[p], sn = cs[half + p];
-    const float x1 = Hh::to_f32(gemm_elem<DTYPE>(ps, t, col0 + i1)), x2 = Hh::to_f32(gemm_elem<DTYPE>(ps, t, col0 + i2));
+  // first trip: the wave's three per-token scalars together (left alone, the compiler fetches each right before its first use,
+  // the row scale behind the wait for the partial sums); second trip: every vector load
+  int64_t pos = positions[t], lc = (int64_t)loc[t];
+  uint32_t sa_bits = __builtin_bit_cast(uint32_t, ps.sa[t]);
+  asm volatile("" : "+s"(pos), "+s"(lc), "+s"(sa_bits));
+  const float sa = __builtin_bit_cast(float, sa_bits);
+  if (w < n_rot) {
+    const int h = w / PC, p = (w % PC) * 64 + lane;
+    const bool is_k = h >= Hq;
+    const int pc = p < half ? p : half - 1;
+    const int i1 = neox ? pc : 2 * pc, i2 = neox ? pc + half : 2 * pc + 1;
+    const int col1 = h * D + i1, col2 = h * D + i2;  // q heads then k heads are contiguous in the qkv row
+    T16* qdst = q_out + t * q_st + (int64_t)h * D;
+    char* kdst = kb + (lc * kb_sn + (int64_t)(h - Hq) * kb_sh) * ES;  // used for a k head only
+    const ElemLoads<SU> l1 = elem_issue<SU>(ps, t, col1), l2 = elem_issue<SU>(ps, t, col2);
+    const float* cs = cache + pos * rot_dim;
+    const float c = cs[pc], sn = cs[half + pc];
+    float b1 = 0.f, b2 = 0.f;
+    if (ps.bias) {
+      b1 = elem_bias<DTYPE>(ps, col1);
+      b2 = elem_bias<DTYPE>(ps, col2);
+    }
+    const float x1 = Hh::to_f32(elem_finish<DTYPE, SU>(ps, l1, sa, b1)), x2 = Hh::to_f32(elem_finish<DTYPE, SU>(ps, l2, sa, b2));
     float r1, r2;
     rope_pair(x1, x2, c, sn, r1, r2);
-    const typename Hh::T o1 = Hh::from_f32(r1), o2 = Hh::from_f32(r2);
-    if (is_k) {
-      pool_store<DTYPE, KV8>(kdst, i1, o1);
-      pool_store<DTYPE, KV8>(kdst, i2, o2);
-    } else {
-      qdst[i1] = o1;
-      qdst[i2] = o2;
+    const T16 o1 = Hh::from_f32(r1), o2 = Hh::from_f32(r2);
+    if (p < half) {
+      if (is_k) {
+        pool_store<DTYPE, KV8>(kdst, i1, o1);
+        pool_store<DTYPE, KV8>(kdst, i2, o2);
+      } else {
+        qdst[i1] = o1;
+        qdst[i2] = o2;
+      }
     }
+    return;
   }
-  for (int i = rot_dim + lane; i < D; i += 64) {  // pass-through dims
-    const typename Hh::T x = gemm_elem<DTYPE>(ps, t, col0 + i);
-    if (is_k) pool_store<DTYPE, KV8>(kdst, i, x); else qdst[i] = x;
-  }
-  if (is_k) {
-    const int vcol0 = (Hq + Hk) * D + (h - Hq) * D;
-    char* vdst = vb + ((int64_t)loc[t] * vb_sn + (int64_t)(h - Hq) * vb_sh) * ES;
-    for (int i = lane; i < D; i += 64) pool_store<DTYPE, KV8>(vdst, i, gemm_elem<DTYPE>(ps, t, vcol0 + i));
+  // copy wave: elements [i0, min(i0 + 64, D)) of head `h` of the qkv row, to q_out (a q head's pass-through) or a pool row
+  w -= n_rot;
+  const bool is_v = w < n_v;
+  if (!is_v) w -= n_v;
+  const int h = is_v ? Hq + Hk + w / VC : w / NC;
+  const int i = (is_v ? (w % VC) * 64 : rot_dim + (w % NC) * 64) + lane;
+  const int ic = i < D ? i : D - 1;
+  const int col = h * D + ic;
+  T16* qdst = q_out + t * q_st + (int64_t)h * D;  // used for h < Hq only
+  char* pdst = nullptr;
+  if (is_v) pdst = vb + (lc * vb_sn + (int64_t)(h - Hq - Hk) * vb_sh) * ES;
+  else if (h >= Hq) pdst = kb + (lc * kb_sn + (int64_t)(h - Hq) * kb_sh) * ES;
+  const ElemLoads<SU> l = elem_issue<SU>(ps, t, col);
+  float b = 0.f;
+  if (ps.bias) b = elem_bias<DTYPE>(ps, col);
+  const T16 x = elem_finish<DTYPE, SU>(ps, l, sa, b);
+  if (i < D) {
+    if (pdst) pool_store<DTYPE, KV8>(pdst, i, x); else qdst[i] = x;
   }
 }
 
@@ -524,6 +565,12 @@ __global__ __launch_bounds__(256) void rope_kv_neox16_kernel(
   }
 }
 
+// The from-partials launchers fetch four slices at a time where there are at most four (see gemm_row8, partials.h)
+#ifndef SGLM_ROWCHAIN_SLICES4
+#define SGLM_ROWCHAIN_SLICES4 1  // 0: always eight at a time (A/B aid, same results)
+#endif
+inline bool slices4_of(const PartialSrc& ps) { return SGLM_ROWCHAIN_SLICES4 && ps.num_slices <= 4; }
+
 // few long rows (decode batches, H >= 4096, at most 2048 vectors of 8): 512 / 1024 threads per row
 // Up to 512 rows (round 4; was 2048): at 1024 prefill rows of 4096 the 256-thread form (two chunks per thread, half the
 // waves per barrier) takes 9.2 us against 10.3 (tools/bench_prefill_elementwise.py); the from-partials form exists up to 128
@@ -602,12 +649,16 @@ int launch_rmsnorm_partials(const PartialSrc& ps, void* residual, const void* we
   using T16 = typename Half16<DTYPE>::T;
   const int nv = (int)(H >> 3);
   const int vpt = (nv + 255) / 256;
-#define RMSP_LAUNCH(V)                                                                                              \
-  hipLaunchKernelGGL((rmsnorm_kernel<DTYPE, V, true>), dim3((unsigned)T), dim3(256), 0, s, (const T16*)nullptr,       \
-                     (T16*)residual, (const T16*)weight, (T16*)out, (uint8_t*)out_q, out_s, (int)H, eps, ps)
-#define RMSP_LAUNCH_W(V, NT_)                                                                                        \
-  hipLaunchKernelGGL((rmsnorm_kernel<DTYPE, V, true, NT_>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr,  \
-                     (T16*)residual, (const T16*)weight, (T16*)out, (uint8_t*)out_q, out_s, (int)H, eps, ps)
+#define RMSP_LAUNCH_W(V, NT_)                                                                                             \
+  do {                                                                                                                    \
+    if (slices4_of(ps))                                                                                                   \
+      hipLaunchKernelGGL((rmsnorm_kernel<DTYPE, V, true, NT_, 1, 4>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr, \
+                         (T16*)residual, (const T16*)weight, (T16*)out, (uint8_t*)out_q, out_s, (int)H, eps, ps);         \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((rmsnorm_kernel<DTYPE, V, true, NT_, 1, 8>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr, \
+                         (T16*)residual, (const T16*)weight, (T16*)out, (uint8_t*)out_q, out_s, (int)H, eps, ps);         \
+  } while (0)
+#define RMSP_LAUNCH(V) RMSP_LAUNCH_W(V, 256)
 #if SGLM_ABL_ROWSPLIT
   if (rms_wide(T, nv) && nv % 256 == 0 && nv <= 1024) {  // four workgroups per row, 256 threads or fewer each
     if (nv <= 512)
@@ -630,6 +681,7 @@ int launch_rmsnorm_partials(const PartialSrc& ps, void* residual, const void* we
   else if (vpt <= 4) RMSP_LAUNCH(4);
   else RMSP_LAUNCH(8);
 #undef RMSP_LAUNCH
+#undef RMSP_LAUNCH_W
   return check_hip(hipGetLastError(), "rmsnorm_from_partials launch");
 }
 
@@ -662,9 +714,15 @@ template <int DTYPE>
 int launch_silu_partials(const PartialSrc& ps, void* out_q, float* out_s, int64_t T, int64_t d, hipStream_t s) {
   using T16 = typename Half16<DTYPE>::T;
   const int nv = (int)(d >> 3);
-#define SILU_P(V, NT_)                                                                                              \
-  hipLaunchKernelGGL((silu_mul_kernel<DTYPE, V, NT_, true>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr, \
-                     (T16*)nullptr, (uint8_t*)out_q, out_s, (int)d, ps)
+#define SILU_P(V, NT_)                                                                                                          \
+  do {                                                                                                                          \
+    if (slices4_of(ps))                                                                                                         \
+      hipLaunchKernelGGL((silu_mul_kernel<DTYPE, V, NT_, true, 1, 4>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr, \
+                         (T16*)nullptr, (uint8_t*)out_q, out_s, (int)d, ps);                                                    \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((silu_mul_kernel<DTYPE, V, NT_, true, 1, 8>), dim3((unsigned)T), dim3(NT_), 0, s, (const T16*)nullptr, \
+                         (T16*)nullptr, (uint8_t*)out_q, out_s, (int)d, ps);                                                    \
+  } while (0)
 #if SGLM_ABL_ROWSPLIT
   if (nv % 1024 == 0 || nv == 448) {  // (448: the 70B TP=8 rank's 3584 columns)
     if (nv == 448)
@@ -1010,15 +1068,23 @@ static int rope_set_kv_partials_impl(int kv8,
                  "rotary_embedding_set_kv_from_partials: null tensor pointer");
   const int64_t N = (num_q_heads + 2 * num_k_heads) * head_size;
   PartialSrc ps{partials, (int)num_slices, num_tokens * N, scales_a, scales_b, bias, (int)N};
-  const int64_t items = num_tokens * (num_q_heads + num_k_heads);
+  // waves per token, as the kernel counts them: 64 pairs, 64 v elements or 64 pass-through elements each
+  const int64_t pc = (rot_dim / 2 + 63) / 64, vc = (head_size + 63) / 64, nc = (head_size - rot_dim + 63) / 64;
+  const int64_t items = num_tokens * ((num_q_heads + num_k_heads) * (pc + nc) + num_k_heads * vc);
   SGLM_CHECK_ARG(items < (1ll << 32), "rotary_embedding_set_kv_from_partials: too many rows");
   const unsigned grid = (unsigned)((items + 3) / 4);
   hipStream_t s = as_stream(stream);
-#define ROPEKVP_(DT, TT, LT, K8)                                                                                         \
-  hipLaunchKernelGGL((rope_kv_from_partials_kernel<DT, LT, K8>), dim3(grid), dim3(256), 0, s, (TT*)q_out, (char*)k_buffer, \
-                     (char*)v_buffer, positions, (const LT*)loc, cos_sin_cache, num_tokens, (int)num_q_heads,             \
-                     (int)num_k_heads, (int)head_size, (int)rot_dim, q_out_stride_t, kb_stride_n, kb_stride_h,            \
-                     vb_stride_n, vb_stride_h, is_neox, ps)
+  const bool s4 = slices4_of(ps);
+#define ROPEKVP_SU(DT, TT, LT, K8, SU_)                                                                                  \
+  hipLaunchKernelGGL((rope_kv_from_partials_kernel<DT, LT, K8, SU_>), dim3(grid), dim3(256), 0, s, (TT*)q_out,            \
+                     (char*)k_buffer, (char*)v_buffer, positions, (const LT*)loc, cos_sin_cache, num_tokens,              \
+                     (int)num_q_heads, (int)num_k_heads, (int)head_size, (int)rot_dim, q_out_stride_t, kb_stride_n,       \
+                     kb_stride_h, vb_stride_n, vb_stride_h, is_neox, ps)
+#define ROPEKVP_(DT, TT, LT, K8)                 \
+  do {                                           \
+    if (s4) ROPEKVP_SU(DT, TT, LT, K8, 4);       \
+    else ROPEKVP_SU(DT, TT, LT, K8, 8);          \
+  } while (0)
 #define ROPEKVP(DT, TT, LT)                 \
   do {                                      \
     if (kv8 == 2) ROPEKVP_(DT, TT, LT, 2);  \
@@ -1032,6 +1098,7 @@ static int rope_set_kv_partials_impl(int kv8,
   }
 #undef ROPEKVP
 #undef ROPEKVP_
+#undef ROPEKVP_SU
   return check_hip(hipGetLastError(), "rotary_embedding_set_kv_from_partials launch");
 }
 
