@@ -34,7 +34,7 @@ extern "C" {
 #define SGL_MI355_ERR_RUNTIME 3          /* a HIP runtime call failed                */
 
 /* ABI version of this header; bumped on any signature change. */
-#define SGL_MI355_ABI_VERSION 17
+#define SGL_MI355_ABI_VERSION 18
 int sgl_mi355_abi_version(void);
 
 /* Copies the calling thread's last error message (NUL-terminated) into buf. Returns its length. */
@@ -448,6 +448,36 @@ int sgl_mi355_int8_scaled_mm_wshuffled(const void* mat_a, const void* mat_b, con
 /* Test aid: the kernel family the last sgl_mi355_int8_scaled_mm* call of the calling thread launched ("int8_stream",
  * "int8_stream_rowmajor", "int8_tiled"; "" before the first call).  Replaces: nothing (like sgl_mi355_fp8_last_kernel). */
 const char* sgl_mi355_int8_last_kernel(void);
+
+/* ------------------------------------------------------------------------------------------
+ * NVFP4 weight-only linear, `petit_nvfp4` (ABI 18): e2m1 weights two per byte (low nibble = even k; sign(1) exp(2)
+ * man(1)), one float8_e4m3fn scale per 16 k, one fp32 global scale, 16-bit activations.
+ * Replaces: petit_kernel.repack_nvfp4 / process_nvfp4_scales (an external package), as called by
+ *           prepare_nvfp4_layer_for_petit, python/sglang/srt/layers/quantization/petit_utils.py:61-75
+ *   Checkpoint layout (petit.py:187-224): weight uint8 [N, K / 2], weight_scale e4m3 [N, K / 16].
+ *   Prepared layout (N % 16 == 0 and K % 128 == 0, else SGL_MI355_ERR_UNSUPPORTED): per 16-column block nb = n / 16 the
+ *   block's [16 rows][K / 32 units] is transposed to [K / 32 units][16 rows], a unit being 32 consecutive k of one row:
+ *     weight byte of (n, k) at ((nb * (K / 32) + k / 32) * 16 + n % 16) * 16 + (k % 32) / 2
+ *     scale  byte of (n, k) at ((nb * (K / 32) + k / 32) * 16 + n % 16) * 2  + (k % 32) / 16
+ *   so that a 128-k step of a block is one contiguous 1-KiB weight piece and one 128-byte scale piece, lane l of a wave
+ *   owning bytes 16 l .. 16 l + 15 and 2 l .. 2 l + 1 of them.  inverse != 0: prepared -> checkpoint bytes.  Not in place. */
+int sgl_mi355_nvfp4_repack(const void* weight, const void* weight_scale, void* weight_out, void* scale_out, int64_t N,
+                           int64_t K, int inverse, void* stream);
+/* Replaces: petit_kernel.mul_nvfp4_a16(a, b, s, global_scale, size_m, size_n, size_k, solution_id) followed by
+ *           output.add_(bias), apply_petit_nvfp4_linear, python/sglang/srt/layers/quantization/petit_utils.py:78-104
+ *   W[n][k] = e2m1(weight[n][k]) * float(weight_scale[n][k / 16])
+ *   out[m][n] = round16(f32(round16(weight_scale_2 * sum_k x[m][k] W[n][k])) + f32(bias[n])); fp32 accumulation over the
+ *   whole of K; without a bias the inner rounding only.  x [M, K] bf16 / fp16 (x_stride_m elements between rows, a
+ *   multiple of 8), weight_scale_2 a DEVICE fp32 scalar, bias [N] in x's dtype or NULL, out [M, N] contiguous in x's
+ *   dtype.  K % 16 == 0 (petit.py:176-179).  prepared != 0: weight / weight_scale in the prepared layout above; 0: the
+ *   checkpoint layout, any N.  `workspace` (fp32, caller-owned, may be NULL unless prepared, M <= 64 and K > 1024) holds
+ *   the split-K partial sums of the weight streamer: ceil(K / 1024) * M * N floats. */
+int sgl_mi355_nvfp4_gemm(const void* x, const void* weight, const void* weight_scale, const float* weight_scale_2,
+                         const void* bias, void* out, float* workspace, int64_t workspace_floats, int64_t M, int64_t N,
+                         int64_t K, int64_t x_stride_m, int prepared, int dtype, void* stream);
+/* Test aid: the kernel family the last sgl_mi355_nvfp4_gemm call of the calling thread launched ("nvfp4_stream",
+ * "nvfp4_tiled", "nvfp4_generic"; "" before the first call).  Replaces: nothing (like sgl_mi355_fp8_last_kernel). */
+const char* sgl_mi355_nvfp4_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------
  * AWQ INT4 (group-wise zero-point) weight-only path.

@@ -29,6 +29,11 @@ def _is_block_scale(param) -> bool:
     return any(c.__name__ == "BlockQuantScaleParameter" for c in type(param).__mro__)
 
 
+def _is_per_tensor_scale(param) -> bool:
+    """``isinstance(param, PerTensorScaleParameter)`` of the reference loaders, for SGLang's class and the local one."""
+    return any(c.__name__ == "PerTensorScaleParameter" for c in type(param).__mro__)
+
+
 class LinearBase(torch.nn.Module):
     # hand-over switches of deferred.py, read on every apply(): class-level defaults so that the lookups never fall through to
     # nn.Module.__getattr__ (a raised AttributeError per miss, ~1 us each, seven per decoder layer in an eager pass)
@@ -71,6 +76,9 @@ class ColumnParallelLinear(LinearBase):
             loaded_weight = loaded_weight.reshape(1)
         if len(self.output_sizes) == 1:
             param.load_column_parallel_weight(loaded_weight, tp_rank=self.tp_rank)
+            return
+        if loaded_shard_id is None and _is_per_tensor_scale(param):  # one scale for the fused matrix: element 0 (:681-688)
+            param.load_merged_column_weight(loaded_weight, shard_id=0, tp_rank=self.tp_rank, tp_size=self.tp_size)
             return
         if loaded_shard_id is None:  # fused on disk: walk the logical sub-matrices (:638-672)
             off = 0
@@ -159,6 +167,9 @@ class QKVParallelLinear(ColumnParallelLinear):
     def weight_loader(self, param, loaded_weight: torch.Tensor, loaded_shard_id=None):
         """linear.py:877-913: shard ids "q" / "k" / "v"; the checkpoint's k / v hold ``total_num_kv_heads`` heads and
         rank r takes head ``r // num_kv_head_replicas``."""
+        if loaded_shard_id is None and _is_per_tensor_scale(param):  # (:884-886)
+            param.load_qkv_weight(loaded_weight, shard_id=0)
+            return
         if loaded_shard_id is None:  # fused qkv on disk (:832-875)
             hs, off = self.head_size, 0
             for sid, n in (("q", self.total_num_heads * hs), ("k", self.total_num_kv_heads * hs),

@@ -1044,6 +1044,87 @@ def int8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> to
     return out
 
 
+# --------------------------------------------------------------------------- NVFP4 weight-only (petit_nvfp4)
+# The two forms of an NVFP4 weight are told apart by structure, like the FP8 and INT8 ones:
+#   checkpoint layout  weight uint8 [N, K / 2],      weight_scale float8_e4m3fn [N, K / 16]      (petit.py:187-224)
+#   prepared layout    weight uint8 [N / 16, 8 K],   weight_scale uint8 [N / 16, K], contiguous  (nvfp4_repack)
+# The prepared scales are bytes on purpose: their dtype is what separates the pairs, whose shapes have the same ratio.
+def nvfp4_repack_supported(N: int, K: int) -> bool:
+    return N > 0 and K > 0 and N % 16 == 0 and K % 128 == 0
+
+
+def _nvfp4_form(weight: torch.Tensor, weight_scale: torch.Tensor, what: str):
+    """(prepared, N, K) of a weight / scale pair in either form; anything else is an error."""
+    if weight.dim() == 2 and weight_scale.dim() == 2 and weight.dtype == torch.uint8 and weight.is_contiguous() \
+            and weight_scale.is_contiguous() and weight.shape[0] == weight_scale.shape[0] and weight.shape[0] > 0:
+        if weight_scale.dtype == torch.float8_e4m3fn and weight.shape[1] == 8 * weight_scale.shape[1] > 0:
+            return False, weight.shape[0], 2 * weight.shape[1]
+        if weight_scale.dtype == torch.uint8 and weight.shape[1] == 8 * weight_scale.shape[1] \
+                and nvfp4_repack_supported(16 * weight.shape[0], weight_scale.shape[1]):
+            return True, 16 * weight.shape[0], weight_scale.shape[1]
+    raise RuntimeError(f"{what}: expected the checkpoint layout (weight uint8 [N, K / 2], weight_scale float8_e4m3fn "
+                       "[N, K / 16]) or the prepared layout of nvfp4_repack (uint8 [N / 16, 8 K], uint8 [N / 16, K]), contiguous; "
+                       f"got {weight.dtype} {tuple(weight.shape)} and {weight_scale.dtype} {tuple(weight_scale.shape)}")
+
+
+def nvfp4_repack(weight: torch.Tensor, weight_scale: torch.Tensor, inverse: bool = False):
+    """Checkpoint layout -> prepared layout (include/sgl_mi355.h "NVFP4": per 16-column block, 32-k units of a row
+    transposed so that a 128-k step is one contiguous 1-KiB weight piece and one 128-byte scale piece); inverse=True
+    restores the checkpoint bytes.  Replaces petit_kernel.repack_nvfp4 + process_nvfp4_scales (petit_utils.py:61-75)."""
+    _need_gpu(weight, weight_scale)
+    prepared, N, K = _nvfp4_form(weight, weight_scale, "nvfp4_repack")
+    if prepared != bool(inverse):
+        raise RuntimeError("nvfp4_repack: the tensors are already in the " + ("prepared" if prepared else "checkpoint") + " layout")
+    if not nvfp4_repack_supported(N, K):
+        raise NotImplementedError(f"nvfp4_repack: the prepared layout needs N % 16 == 0 and K % 128 == 0, got N={N} K={K}")
+    if inverse:
+        w = torch.empty((N, K // 2), dtype=torch.uint8, device=weight.device)
+        s = torch.empty((N, K // 16), dtype=torch.float8_e4m3fn, device=weight.device)
+    else:
+        w = torch.empty((N // 16, 8 * K), dtype=torch.uint8, device=weight.device)
+        s = torch.empty((N // 16, K), dtype=torch.uint8, device=weight.device)
+    _lib.check(_lib.lib().sgl_mi355_nvfp4_repack(_ptr(weight), _ptr(weight_scale), _ptr(w), _ptr(s), _I64(N), _I64(K),
+                                                 _I(1 if inverse else 0), _stream(weight)))
+    return w, s
+
+
+def nvfp4_last_kernel() -> str:
+    """Kernel family launched by this thread's last nvfp4_gemm call (test aid)."""
+    f = _lib.lib().sgl_mi355_nvfp4_last_kernel
+    f.restype = ctypes.c_char_p
+    return f().decode()
+
+
+def nvfp4_gemm(x, weight, weight_scale, weight_scale_2, bias=None) -> torch.Tensor:
+    """petit_kernel.mul_nvfp4_a16(a, b, s, global_scale, ...) then output.add_(bias) (petit_utils.py:78-104):
+    out = round16(fp32(round16(weight_scale_2 * x @ W^T)) + fp32(bias)), W = e2m1(weight) * weight_scale per 16 k, fp32
+    accumulation.  x [M, K] fp16 / bf16; weight / weight_scale in the checkpoint or the prepared layout (told apart by
+    structure, see above); weight_scale_2 a float32 device scalar."""
+    _need_gpu(x, weight, weight_scale, weight_scale_2, bias)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError("nvfp4_gemm: x must be a row major 2D tensor")
+    dtype = _dtype_code(x)
+    prepared, N, K = _nvfp4_form(weight, weight_scale, "nvfp4_gemm")
+    M = x.shape[0]
+    if x.shape[1] != K:
+        raise RuntimeError(f"nvfp4_gemm: x has {x.shape[1]} columns, the weight has K = {K}")
+    if K % 16 != 0:
+        raise RuntimeError("Unsupported model when in features size is not multiple of 16")  # petit.py:176-179
+    if weight_scale_2.dtype != torch.float32 or weight_scale_2.numel() != 1:
+        raise RuntimeError("nvfp4_gemm: weight_scale_2 must be one float32 value")
+    if bias is not None and (bias.numel() != N or bias.dtype != x.dtype or not bias.is_contiguous()):
+        raise RuntimeError("nvfp4_gemm: bias must be a contiguous [N] tensor of x's dtype")
+    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    # the M <= 64 weight streamer cuts K into slices of 1024 (gemm_nvfp4.hip: its LDS capacity) and keeps fp32 partial sums
+    slices = -(-K // 1024) if prepared and 0 < M <= 64 else 1
+    ws = _fp8_workspace.get(x.device, slices * M * N) if slices > 1 else None
+    _lib.check(_lib.lib().sgl_mi355_nvfp4_gemm(
+        _ptr(x), _ptr(weight), _ptr(weight_scale), _ptr(weight_scale_2), _ptr(bias), _ptr(out), _ptr(ws),
+        _I64(ws.numel() if ws is not None else 0), _I64(M), _I64(N), _I64(K), _I64(x.stride(0) if M > 1 else K),
+        _I(1 if prepared else 0), _I(dtype), _stream(x)))
+    return out
+
+
 def fp8_scaled_mm_silu_mul(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None) -> Optional[torch.Tensor]:
     """silu_and_mul(fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias)) in ONE launch -- the gate_up GEMM of a
     gated MLP (mat_b = [gate | up] columns) with the activation in its epilogue: [M, N/2], bit-identical to the two calls.

@@ -135,6 +135,36 @@ class BlockQuantScaleParameter(_ColumnvLLMParameter, RowvLLMParameter):
     row-shardable; the layers hand it shard offsets and sizes in BLOCK units (linear.py:702-710, 899-903)."""
 
 
+class PerTensorScaleParameter(BasevLLMParameter):
+    """One scale per logical matrix of a fused layer (parameter.py:308-380; for qkv three are loaded from disk): a shard
+    id -- an index, or "q" / "k" / "v" -- picks the element a merged or qkv layer's checkpoint scalar goes to; row- and
+    column-parallel layers load the tensor as it is.  What becomes of the elements is the quant method's business
+    (process_weights_after_loading)."""
+
+    _QKV = {"q": 0, "k": 1, "v": 2}
+
+    def _load_into_shard_id(self, loaded_weight, shard_id, **kw):
+        if not isinstance(shard_id, int):
+            assert shard_id in self._QKV, f"shard id {shard_id!r} is neither an index nor one of q / k / v"
+            shard_id = self._QKV[shard_id]
+        if loaded_weight.dim() != 0:  # scales written with a shape (compressed-tensors) hold one element
+            assert loaded_weight.shape[0] == 1
+            loaded_weight = loaded_weight[0]
+        self._copy_exact(self.data[shard_id], loaded_weight)
+
+    def load_merged_column_weight(self, loaded_weight, shard_id=0, **kw):
+        self._load_into_shard_id(loaded_weight, shard_id)
+
+    def load_qkv_weight(self, loaded_weight, shard_id=0, **kw):
+        self._load_into_shard_id(loaded_weight, shard_id)
+
+    def load_column_parallel_weight(self, loaded_weight, **kw):
+        self._copy_exact(self.data, loaded_weight)
+
+    def load_row_parallel_weight(self, loaded_weight, **kw):
+        self._copy_exact(self.data, loaded_weight)
+
+
 class PackedvLLMParameter(ModelWeightParameter):
     """Weights packed several to a word along ``packed_dim`` (parameter.py:416-458): shard offsets and
     sizes given in logical columns are divided by ``packed_factor`` before slicing."""
@@ -214,7 +244,7 @@ _LOCAL = SimpleNamespace(
     BasevLLMParameter=BasevLLMParameter, _ColumnvLLMParameter=_ColumnvLLMParameter, RowvLLMParameter=RowvLLMParameter,
     ModelWeightParameter=ModelWeightParameter, GroupQuantScaleParameter=GroupQuantScaleParameter,
     ChannelQuantScaleParameter=ChannelQuantScaleParameter, BlockQuantScaleParameter=BlockQuantScaleParameter,
-    PackedvLLMParameter=PackedvLLMParameter, source="local")
+    PackedvLLMParameter=PackedvLLMParameter, PerTensorScaleParameter=PerTensorScaleParameter, source="local")
 _cached = None
 
 
@@ -230,7 +260,8 @@ def classes(refresh: bool = False):
             BasevLLMParameter=m.BasevLLMParameter, _ColumnvLLMParameter=m._ColumnvLLMParameter,
             RowvLLMParameter=m.RowvLLMParameter, ModelWeightParameter=m.ModelWeightParameter,
             GroupQuantScaleParameter=m.GroupQuantScaleParameter, ChannelQuantScaleParameter=m.ChannelQuantScaleParameter,
-            BlockQuantScaleParameter=m.BlockQuantScaleParameter, PackedvLLMParameter=m.PackedvLLMParameter, source="sglang")
+            BlockQuantScaleParameter=m.BlockQuantScaleParameter, PackedvLLMParameter=m.PackedvLLMParameter,
+            PerTensorScaleParameter=m.PerTensorScaleParameter, source="sglang")
     except Exception:  # SGLang absent or not importable in this process: same-named local classes
         _cached = _LOCAL
     return _cached

@@ -7,6 +7,7 @@ Interface mirrored (same method names / argument meaning):
   Fp8Config / Fp8LinearMethod (block FP8)   python/sglang/srt/layers/quantization/fp8.py:110-190, 221-361, 462-480
   apply_fp8_linear                          python/sglang/srt/layers/quantization/fp8_utils.py:510-533,653-704
   AWQConfig / AWQLinearMethod               python/sglang/srt/layers/quantization/awq.py:75-150,319-418
+  PetitNvFp4Config / PetitNvFp4LinearMethod python/sglang/srt/layers/quantization/petit.py:33-252, petit_utils.py:36-104
   QUANTIZATION_METHODS registry             python/sglang/srt/layers/quantization/__init__.py:74-121
 
 ``create_weights`` registers the same attributes on the layer (``weight``, ``weight_scale`` /
@@ -749,7 +750,120 @@ class AWQLinearMethod(LinearMethodBase):
         return out.reshape(out_shape)
 
 
+# ----------------------------------------------------------------------------- NVFP4 weight-only (petit_nvfp4)
+class PetitNvFp4Config(QuantizationConfig):
+    """petit.py:33-131: the ModelOpt NVFP4 checkpoint format (e2m1 weights, e4m3 scales per 16, one fp32 global scale) with
+    16-bit activations.  On ROCm every ``quant_method: "modelopt"`` checkpoint is turned into this method."""
+
+    def __init__(self, is_checkpoint_nvfp4_serialized: bool = False, kv_cache_quant_algo: Optional[str] = None,
+                 group_size: Optional[int] = None, exclude_modules: Optional[List[str]] = None):
+        self.is_checkpoint_nvfp4_serialized = is_checkpoint_nvfp4_serialized
+        self.group_size, self.kv_cache_quant_algo, self.exclude_modules = group_size, kv_cache_quant_algo, exclude_modules
+
+    @classmethod
+    def get_name(cls) -> str:
+        return "petit_nvfp4"
+
+    @classmethod
+    def get_supported_act_dtypes(cls):
+        return [torch.bfloat16, torch.half]
+
+    @classmethod
+    def get_min_capability(cls) -> int:
+        return 90
+
+    @classmethod
+    def get_config_filenames(cls):
+        return ["hf_quant_config.json"]
+
+    @classmethod
+    def from_config(cls, config):
+        if "quantization" not in config:
+            raise ValueError("Cannot find any of ['quantization'] in the model's quantization config.")
+        quant_config = config["quantization"]
+        quant_method, group_size = quant_config["quant_algo"], quant_config.get("group_size", None)
+        if quant_method != "NVFP4":  # petit_utils.py:36-58
+            raise ValueError("Petit currently only supports: NVFP4 quantizations in sglang. Please check the "
+                             "`hf_quant_config.json` file for your model's quant configuration.")
+        if group_size is not None and group_size != 16:
+            raise ValueError("Petit currently only supports: group_size=16 quantizations.")
+        kv_cache_quant_algo = quant_config["kv_cache_quant_algo"] or "auto"
+        exclude_modules = quant_config.get("exclude_modules", None)
+        if not (group_size and kv_cache_quant_algo and (exclude_modules is not None)):
+            raise ValueError("NVFP4 quantization requires group size and kv_cache_quant_algo specified in hf_quant_config.json")
+        return cls(True, kv_cache_quant_algo, group_size, exclude_modules)
+
+    @classmethod
+    def override_quantization_method(cls, hf_quant_cfg, user_quant) -> Optional[str]:
+        return cls.get_name() if cls.is_petit_nvfp4_compatible(hf_quant_cfg) else None
+
+    @classmethod
+    def is_petit_nvfp4_compatible(cls, quant_config: Dict[str, Any]) -> bool:
+        return torch.version.hip is not None and quant_config.get("quant_method", "").lower() == "modelopt"
+
+    def is_layer_excluded(self, prefix: str, exclude_modules: List[str]) -> bool:
+        return any(re.fullmatch(p.replace(".", r"\.").replace("*", r".*"), prefix) for p in exclude_modules)
+
+    def get_quant_method(self, layer, prefix: str):
+        if is_linear_layer(layer):
+            if prefix in self.exclude_modules or self.is_layer_excluded(prefix, self.exclude_modules):
+                return UnquantizedLinearMethod()
+            return PetitNvFp4LinearMethod(self)
+        return None
+
+
+class PetitNvFp4LinearMethod(LinearMethodBase):
+    """petit.py:134-252: ``weight`` uint8 [N, K / 2] (two e2m1 per byte), ``weight_scale`` e4m3 [N, K / 16], ``weight_scale_2``
+    and ``input_scale`` fp32, one per logical shard; apply = ops.nvfp4_gemm (csrc/gemm_nvfp4.hip), one launch (two below 65
+    rows when K > 1024)."""
+
+    def __init__(self, quant_config: PetitNvFp4Config):
+        self.quant_config = quant_config
+
+    def create_weights(self, layer, input_size_per_partition, output_partition_sizes, input_size, output_size,
+                       params_dtype, **extra_weight_attrs):
+        if not self.quant_config.is_checkpoint_nvfp4_serialized:
+            raise ValueError("NVFP4 quantization was selected,  dynamic quantization is not supported.")
+        P = _param_classes()
+        weight_loader = extra_weight_attrs.get("weight_loader")
+        n = sum(output_partition_sizes)
+        layer.logical_widths = output_partition_sizes
+        layer.input_size_per_partition, layer.output_size_per_partition = input_size_per_partition, n
+        if input_size_per_partition % 16 != 0:
+            raise ValueError("Unsupported model when in features size is not multiple of 16")
+        layer.register_parameter("weight", P.ModelWeightParameter(
+            data=torch.empty(n, input_size_per_partition // 2, dtype=torch.uint8), input_dim=1, output_dim=0,
+            weight_loader=weight_loader))
+        layer.register_parameter("input_scale", P.PerTensorScaleParameter(
+            data=torch.empty(len(output_partition_sizes), dtype=torch.float32), weight_loader=weight_loader))
+        layer.register_parameter("weight_scale_2", P.PerTensorScaleParameter(
+            data=torch.empty(len(output_partition_sizes), dtype=torch.float32), weight_loader=weight_loader))
+        layer.register_parameter("weight_scale", P.ModelWeightParameter(
+            data=torch.empty(n, input_size_per_partition // self.quant_config.group_size, dtype=torch.float8_e4m3fn),
+            input_dim=1, output_dim=0, weight_loader=weight_loader))
+
+    def process_weights_after_loading(self, layer) -> None:
+        if getattr(layer, "_sgl_mi355_nvfp4_done", False):
+            return  # re-entered: the bytes are already laid out and the storage must not change
+        # petit.py:227-236: one global scale for the fused matrix, the largest of its shards'; activations stay 16-bit, so
+        # input_scale (and the alpha made of it) has no use and goes
+        layer.weight_scale_2 = torch.nn.Parameter(layer.weight_scale_2.max().to(torch.float32), requires_grad=False)
+        del layer.input_scale
+        weight, scale = layer.weight.data, layer.weight_scale.data
+        n, k = weight.shape[0], 2 * weight.shape[1]
+        if PRESHUFFLE_FP8_WEIGHTS and weight.is_cuda and ops.nvfp4_repack_supported(n, k):
+            weight, scale = ops.nvfp4_repack(weight.contiguous(), scale.contiguous())
+        layer.weight = torch.nn.Parameter(weight, requires_grad=False)
+        layer.weight_scale = torch.nn.Parameter(scale, requires_grad=False)
+        layer._sgl_mi355_nvfp4_done = True
+
+    def apply(self, layer, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        out = ops.nvfp4_gemm(x.reshape(-1, x.shape[-1]), layer.weight, layer.weight_scale, layer.weight_scale_2, bias)
+        return out.view(*x.shape[:-1], out.shape[-1])
+
+
 QUANTIZATION_METHODS = {
+    "petit_nvfp4": PetitNvFp4Config,
     "w8a8_fp8": W8A8Fp8Config,
     "fp8": Fp8Config,
     "w8a8_int8": W8A8Int8Config,
